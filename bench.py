@@ -29,9 +29,12 @@ Workloads (--config, BASELINE.json configs[i]; all synthetic, generated in HBM):
 Extra objects on the JSON line: ``roofline`` (dominant kernel: its execution span measured
 inside the kernel, first wavefront start to last wavefront end, = a kernel trace's
 duration; traffic and VALU counts from the committed PMC pass of this command when one
-exists), ``roofline_cdc`` (the scan kernel), ``cpu_baseline`` (C restatement of the
+exists), ``roofline_cdc`` (the scan kernel).  A plain run does no more than its timed steps
+need.  With ``--full``, after the timed steps: ``cpu_baseline`` (C restatement of the
 reference chunker on the host threads the box allots, rank 0 at N=1), ``e2e`` (pinned host
-input incl. PCIe H2D, c2 only), ``parity`` (GPU records == CPU oracle records on a sample).
+input incl. PCIe H2D, c2 only), ``parity`` (GPU records == CPU oracle records on a sample)
+and the other side measurements (``chain_floor``, ``two_in_flight``, ``configs1_literal``).
+``--dump-outputs DIR`` writes the records of the last timed step as DIR/<name>.npy.
 """
 import argparse
 import os
@@ -120,6 +123,16 @@ def parse():
     ap.add_argument("--commit-hash", default="fused", choices=["fused", "separate"],
                     help="--path commit: DataRef hashes in one launch with the chunks' content "
                          "hashes (pfscdc_commit_refs), or the scan's own hash pass first")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement and check "
+                         "(cpu_baseline, parity, e2e, chain_floor, two_in_flight, "
+                         "configs1_literal, the isolated steps, single_commit, one_context, "
+                         "host_memcpy_gb_s); the --no-* options below drop single ones.  Without "
+                         "it a run sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as "
+                         "DIR/<name>.npy (float64, at most 64 MB in all; larger outputs as a "
+                         "fixed seeded sample of their rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-chain-floor", action="store_true",

@@ -7,7 +7,7 @@ import hashlib
 import time
 
 from . import parity as par
-from .common import C3_BYTES, METRIC, med, workload
+from .common import C3_BYTES, METRIC, dump_outputs, med, workload
 from .harness import Harness
 
 
@@ -59,7 +59,9 @@ def bench_c3_split(args, ctx):
                  index_segments=int(len(segs)),
                  note="hash_ms: this rank's segments (a split stream is bound by its longest "
                       "serial BLAKE2b chains, up to max = 20 MB)")
-    if rank == 0:
+    if args.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, {"segments": segs})
+    if args.full and rank == 0:
         out["parity"] = par.stream_border_parity(segs, n, ranges, seed, params)
     H.emit(out)
     H.close()

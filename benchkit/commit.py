@@ -15,7 +15,7 @@ import hashlib
 import threading
 import time
 
-from .common import HBM_PEAK_GBS, Work, fill, workload
+from .common import HBM_PEAK_GBS, Work, dump_outputs, fill, workload
 from .harness import Harness, plan_steps
 
 
@@ -197,7 +197,11 @@ def bench_commit(args, ctx):
     if S > 1:
         out["note"] = ("kernel_ms are per step on its own stream; with %d steps in flight they "
                        "overlap, so ms_per_step < their sum" % S)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs and rank == 0:
+        # the commit's chunk list and DataRef hashes as the last step returned them
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs,
+                                             {"chunks": chunks, "dataref_hashes": dr_hashes})
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if in_place:  # the buffer holds the verification step's ciphertext
             fill(chunkers[0], data, work)
         out["parity"] = commit_parity(data, work, streams, last, params, np)

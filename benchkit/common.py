@@ -198,6 +198,48 @@ def med(xs):
     return round(statistics.median(xs), 4) if xs else None
 
 
+DUMP_BUDGET = 64 << 20  # --dump-outputs: bytes written in all
+
+
+def as_float_array(a):
+    """A record or integer array as float64, exactly: a structured array becomes one row per
+    record with one column per scalar (a (32,) byte field is 32 columns); every value the
+    paths produce (bytes, counts, offsets below 2^53) is exact in float64."""
+    import numpy as np
+    a = np.asarray(a)
+    if a.dtype.kind == "V" and a.dtype.names is None:  # opaque bytes (np.void records)
+        a = a.view(np.uint8).reshape(len(a), -1)
+    if a.dtype.names:
+        cols = [as_float_array(a[f]) for f in a.dtype.names]
+        return np.concatenate([c.reshape(len(a), c.size // max(len(a), 1)) for c in cols], axis=1)
+    if a.dtype.kind in "ui":
+        assert a.size == 0 or int(a.max()) < 1 << 53, "not exact in float64"
+    return a.astype(np.float64)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: array} of the last timed step as DIR/<name>.npy (float64), at
+    most DUMP_BUDGET bytes in all.  An output larger than its equal share of the budget is
+    written as a fixed sample of its rows (seeded, sorted, the same from run to run).  Returns
+    what was written, for the result line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(len(arrays), 1)
+    done = {}
+    for name, a in arrays.items():
+        f = np.ascontiguousarray(as_float_array(a))
+        rows = f.shape[0] if f.ndim else 1
+        row_bytes = max(f.nbytes // max(rows, 1), 8)
+        keep = share // row_bytes
+        if f.ndim and rows > keep:
+            pick = np.sort(np.random.default_rng(0x0D).choice(rows, size=keep, replace=False))
+            f = f[pick]
+        np.save(os.path.join(dirname, name + ".npy"), f)
+        done[name] = {"rows": int(f.shape[0]) if f.ndim else 1, "of": int(rows),
+                      "dtype": str(f.dtype)}
+    return done
+
+
 def host_memcpy_rate(torch, nbytes):
     """The ceiling of the Put copy: a large host-to-page-locked copy on the job's threads
     (torch's parallel CPU copy, OMP_NUM_THREADS), best of 3, GB/s."""

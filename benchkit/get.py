@@ -1,7 +1,7 @@
 """Read path (chunk.Get, transform.go:50-78): the step's segments are stored chunks (the
 chunk.Create form); one step = pfscdc_get_chunks over all of them (verify BLAKE2b of the
 stored bytes against Ref.Id, ChaCha20 decrypt), device-resident in and out."""
-from .common import HBM_PEAK_GBS, med
+from .common import DUMP_BUDGET, HBM_PEAK_GBS, dump_outputs, med
 from .harness import Harness
 
 
@@ -47,6 +47,16 @@ def bench_get(args, ctx, chunker, data, work):
                             "avg_launch_ms": round(ms, 4), "kernel": "blake2b_kernel<kModeGet>"},
                   parity={"all_chunks_verified": bool(ok.all()),
                           "plaintext_equals_original": same})
+    if args.dump_outputs and ctx["rank"] == 0:
+        # the verify flags of every chunk, and the decrypted bytes (a fixed seeded sample of
+        # their positions when they exceed the budget's share)
+        plain = out
+        keep = DUMP_BUDGET // 2 // 8
+        if out.numel() > keep:
+            pick = np.sort(np.random.default_rng(0x0D).integers(0, out.numel(), size=keep))
+            plain = out[torch.from_numpy(pick).to(out.device)]
+        line["dumped_outputs"] = dump_outputs(
+            args.dump_outputs, {"ok": np.asarray(ok), "plaintext": plain.cpu().numpy()})
     H.emit(line)
     H.close()
     chunker.close()

@@ -7,7 +7,7 @@ contexts on the one GPU).  Beside the group's line: one context alone over the s
 the gathered index's digest against it."""
 import hashlib
 
-from .common import GIB, med
+from .common import GIB, dump_outputs, med
 from .harness import Harness
 
 
@@ -42,7 +42,7 @@ def bench_group(args, ctx):
         r = last["r"]
         digest = hashlib.blake2b(r.segments.tobytes() + r.file_begin.tobytes(),
                                  digest_size=16).hexdigest()
-        out = {"elapsed": elapsed, "digest": digest, "segments": int(len(r.segments)),
+        out = {"elapsed": elapsed, "digest": digest, "result": r, "segments": int(len(r.segments)),
                "part_begin": [int(x) for x in g.part_begin()],
                "member_ms": [med([t["member_ms"][k] for t in tm]) for k in range(len(devs))],
                "gather_ms": med([t["gather_ms"] for t in tm]),
@@ -53,7 +53,8 @@ def bench_group(args, ctx):
         return out
 
     grp = run_group(members, args.steps, args.warmup)
-    one = run_group([members[0]], args.steps, args.warmup)
+    # beside it (--full): one context alone over the same files
+    one = run_group([members[0]], args.steps, args.warmup) if args.full else None
     info = {"workload": "configs[1] batches of %d x %d B, %d per step, resident on the members"
                         % (args.files, args.file_bytes, batches),
             "path": "group (pfscdc_group_scan_resident: dealt scan + hash, peer-to-peer gather)",
@@ -64,10 +65,15 @@ def bench_group(args, ctx):
                   total, args.steps, args.warmup, grp["elapsed"], "strong", info,
                   member_ms=grp["member_ms"], gather_ms=grp["gather_ms"],
                   gather_bytes=grp["gather_bytes"], segments=grp["segments"],
-                  one_context={"value": round(total * args.steps / one["elapsed"] / GIB, 3),
+                  parity={"index_digest": grp["digest"]})
+    if one:
+        line["one_context"] = {"value": round(total * args.steps / one["elapsed"] / GIB, 3),
                                "unit": "GiB/s", "ms_per_step": round(one["elapsed"] * 1e3 /
                                                                      max(args.steps, 1), 3),
-                               "device": members[0]},
-                  parity={"index_digest": grp["digest"],
-                          "equals_one_context": grp["digest"] == one["digest"]})
+                               "device": members[0]}
+        line["parity"]["equals_one_context"] = grp["digest"] == one["digest"]
+    if args.dump_outputs:
+        r = grp["result"]
+        line["dumped_outputs"] = dump_outputs(args.dump_outputs,
+                                              {"segments": r.segments, "file_begin": r.file_begin})
     H.emit(line)

@@ -8,7 +8,8 @@ import time
 
 from . import parity as par
 from .common import (GIB, HBM_PEAK_GBS, LITERAL_INFLIGHT, METRIC, SIMDS, VALU_PEAK_GIPS,
-                     C3_INFLIGHT, C3_SCAN_GRID, fill, hit_rate, load_traffic, med, workload)
+                     C3_INFLIGHT, C3_SCAN_GRID, dump_outputs, fill, hit_rate, load_traffic, med,
+                     workload)
 from .harness import Harness, plan_steps, steady_state
 
 
@@ -99,6 +100,7 @@ def bench_put(args, ctx, c3s):
         if record:
             steps_t.append(chunkers[k].timings())
             done_at.append(time.perf_counter())
+            last["timed"] = res  # the timed region's last step, whichever context ran it
         last[k] = res
         return res
 
@@ -235,10 +237,20 @@ def bench_put(args, ctx, c3s):
         out["steps_rule"] = steps_note
     if rvalu:
         out["roofline_valu"] = rvalu
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path got back from its last timed step on this rank
+        fin = last.get("timed", res)
+        arrays = {"segments": fin.segments, "file_begin": fin.file_begin}
+        if fin.refs is not None:
+            arrays["refs"] = fin.refs
+        if world > 1 and "index" in last:  # the chunk-ref index gathered from every rank
+            arrays["index"] = last["index"]
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, arrays)
     if S > 1:
         # the rate once the pipeline is full (the whole-region value above includes the fill
         # and the drain: with every stream started at t0 they end together, a burst)
         out["steady_state"] = steady_state(H.t0, done_at, S, total * world)
+    if S > 1 and args.full:
         # after the timed region: steps alone on the GPU (median of 3), so the kernels' own
         # durations can be read beside the overlapped ones above
         iso, walls = [], []
@@ -260,7 +272,7 @@ def bench_put(args, ctx, c3s):
                                     "note": "median of 3 steps with nothing else in flight, "
                                             "after the timed region"}
 
-    if args.config in ("c4", "c5") and work.group > 1:
+    if args.full and args.config in ("c4", "c5") and work.group > 1:
         # the literal configuration beside the grouped one: ONE commit per step over the N GPUs
         # (copy 0 of this rank's share: strong scaling, bound by its longest chains)
         out["single_commit"] = single_commit(args, work, chunkers[0], batches[0], H)
@@ -302,7 +314,7 @@ def bench_put(args, ctx, c3s):
     del batches[1:]
     torch.cuda.empty_cache()
 
-    solo = rank == 0 and world == 1 and not args.shard
+    solo = args.full and rank == 0 and world == 1 and not args.shard
     if solo and not args.no_chain_floor:
         out["chain_floor"] = chain_floor(res, hash_ms, data, params, local, Chunker)
     if solo and args.config == "c2" and S == 1 and not args.no_pipelined:
@@ -314,7 +326,8 @@ def bench_put(args, ctx, c3s):
         out["e2e"] = e2e(args, work, data, params, local, Chunker, torch)
     if solo and not args.no_cpu_baseline:
         par.cpu_baseline(args, work, data, res, params, out, last)
-    elif rank == 0 and args.config in ("c2", "c4", "c5") and "index" in last and not args.shard:
+    elif args.full and rank == 0 and args.config in ("c2", "c4", "c5") and "index" in last \
+            and not args.shard:
         # every N: the first and last piece of every rank regenerated here and run through
         # the oracle, vs the gathered index (no bytes move between ranks)
         out["parity"] = par.sample_parity(args, world, last["index"], work.seed, work.mode,

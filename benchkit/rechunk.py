@@ -4,6 +4,7 @@ fileset/merge.go:125-143, chunk/writer.go:315-420): a 1 GiB file written by
 store), then the merged file's hash: Copy of every DataRef through a fresh writer, whole
 aligned chunks passed through, the rest read back (chunk.Get on the GPU) and re-rolled.
 Checked against the single-writer hash (the reference's TestStableHash property)."""
+from .common import dump_outputs
 from .harness import Harness
 
 
@@ -57,5 +58,9 @@ def bench_rechunk(args, ctx):
                  H.sum_over_ranks(nbytes), args.steps, args.warmup, elapsed, "weak", info,
                  data="synthetic (seeded splitmix64 bytes generated in HBM, copied to host)",
                  parity={"merged_hash_equals_single_writer_hash": last.get("got") == want})
+    if args.dump_outputs and ctx["rank"] == 0:
+        import numpy as np
+        got = np.frombuffer(bytes(last["got"]), dtype=np.uint8) if args.steps > 0 else np.zeros(0)
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, {"merged_file_hash": got})
     H.emit(out)
     H.close()

@@ -7,7 +7,7 @@ gathered: the same list as one writer's.  Reference: fileset/unordered_writer.go
 import hashlib
 import time
 
-from .common import Work, c4_sizes, fill, host_memcpy_rate, workload
+from .common import Work, c4_sizes, dump_outputs, fill, host_memcpy_rate, workload
 from .harness import Harness
 
 
@@ -107,6 +107,12 @@ def bench_uw(args, ctx):
                              "(pfscdc_uw_timings)" % _lib.get_knob("PFSCDC_UW_WORKERS"))
     if stages.get("put_copy"):
         out["put_copy_gb_s"] = round(nbytes / (stages["put_copy"] * 1e-3) / 1e9, 2)
+    if stages.get("put_copy") and args.full:
         out["host_memcpy_gb_s"] = host_memcpy_rate(torch, min(nbytes, 4 << 30))
+    if args.dump_outputs and ctx["rank"] == 0:
+        # the commit's fileset roots (additive, deletive, size) in their serialized form
+        enc = b"".join(pd.encode_primitive(*g) for g in gathered)
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs,
+                                             {"filesets": np.frombuffer(enc, dtype=np.uint8)})
     H.emit(out)
     H.close()

@@ -264,8 +264,8 @@ def test_cgo_stub_never_rehashes_on_the_host():
     assert "CreateWithID(" in code
 
 
-def _apply_hunk(text, hunk):
-    """Apply one unified-diff hunk (context/removals must match exactly) to text."""
+def _hunk_sides(hunk):
+    """(old, new) text of one unified-diff hunk."""
     old, new = [], []
     for line in hunk.splitlines():
         if line.startswith(("---", "+++", "@@")):
@@ -275,28 +275,78 @@ def _apply_hunk(text, hunk):
             old.append(body)
         if tag in " +":
             new.append(body)
-    old_s, new_s = "\n".join(old) + "\n", "\n".join(new) + "\n"
+    return "\n".join(old) + "\n", "\n".join(new) + "\n"
+
+
+def _apply_hunk(text, hunk):
+    """Apply one unified-diff hunk (context/removals must match exactly) to text."""
+    old_s, new_s = _hunk_sides(hunk)
     assert text.count(old_s) == 1, "hunk context does not match client.go"
     return text.replace(old_s, new_s)
 
 
 REF_CLIENT = "/root/reference/src/internal/storage/chunk/client.go"
+CLIENT_FACTS = os.path.join(ROOT, "tests", "golden", "client_go_facts.json")
+GET_HEADER = "func (c *trackedClient) Get("
+# what the checks below look for in the patched file
+NEEDLES = ("Hash(chunkData)", "chunkID :=", "c.store.Put(ctx, key, chunkData)",
+           "func (c *trackedClient) Create(", "func (c *trackedClient) CreateWithID(")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CLIENT), reason="reference tree not present")
-def test_create_with_id_patch_applies():
-    """The one reference-side patch (INTEGRATION.md) applies to chunk/client.go as it lies in
-    the reference, keeps Create's behaviour (Create = CreateWithID(Hash(chunkData))) and
-    leaves the hash nowhere else."""
-    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    (hunk,) = re.findall(r"```diff\n(.*?)```", doc, flags=re.S)
-    assert "a/src/internal/storage/chunk/client.go" in hunk
-    out = _apply_hunk(open(REF_CLIENT).read(), hunk)
+def client_go_facts(text, old_s):
+    """What the patch check needs to know of client.go, as counts and a digest (recorded in
+    tests/golden/client_go_facts.json; none of the file's text): how often the hunk's old side
+    occurs, its SHA-256, and how often each needle occurs before it, between it and Get's
+    header, and from there on."""
+    import hashlib
+    at = text.index(old_s)
+    end = at + len(old_s)
+    get = text.index(GET_HEADER, end)
+    return {"old_side_occurrences": text.count(old_s),
+            "old_side_sha256": hashlib.sha256(old_s.encode()).hexdigest(),
+            "before_old_side": {n: text[:at].count(n) for n in NEEDLES},
+            "between_old_side_and_get": {n: text[end:get].count(n) for n in NEEDLES},
+            "from_get_on": {n: text[get:].count(n) for n in NEEDLES}}
+
+
+def _check_patched_client(out):
     assert out.count("Hash(chunkData)") == 1
     create = out[out.index("func (c *trackedClient) Create("):out.index("func (c *trackedClient) CreateWithID(")]
     assert "return c.CreateWithID(ctx, md, Hash(chunkData), chunkData)" in create
-    with_id = out[out.index("func (c *trackedClient) CreateWithID("):out.index("func (c *trackedClient) Get(")]
+    with_id = out[out.index("func (c *trackedClient) CreateWithID("):out.index(GET_HEADER)]
     assert "chunkID :=" not in with_id and "c.store.Put(ctx, key, chunkData)" in with_id
+
+
+def test_create_with_id_patch_applies():
+    """The one reference-side patch (INTEGRATION.md) applies to chunk/client.go as it lies in
+    the reference, keeps Create's behaviour (Create = CreateWithID(Hash(chunkData))) and
+    leaves the hash nowhere else.  client.go itself is not part of this repository: the hunk's
+    old side is held against the recorded digest of the one place it occurs in client.go, and
+    the rest of the file stands in as the recorded counts of what the checks look for.  Where
+    the reference tree is at hand, the record is checked against it and the hunk applied to
+    the file itself."""
+    import hashlib
+    import json
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    (hunk,) = re.findall(r"```diff\n(.*?)```", doc, flags=re.S)
+    assert "a/src/internal/storage/chunk/client.go" in hunk
+    old_s, _ = _hunk_sides(hunk)
+    facts = json.load(open(CLIENT_FACTS))
+    assert facts["old_side_occurrences"] == 1, "hunk context does not match client.go"
+    assert hashlib.sha256(old_s.encode()).hexdigest() == facts["old_side_sha256"], \
+        "hunk context does not match client.go"
+
+    def stand_in(counts):
+        return "".join((n + "\n") * k for n, k in counts.items())
+
+    text = stand_in(facts["before_old_side"]) + old_s + \
+        stand_in(facts["between_old_side_and_get"]) + GET_HEADER + "\n" + \
+        stand_in(facts["from_get_on"])
+    _check_patched_client(_apply_hunk(text, hunk))
+    if os.path.exists(REF_CLIENT):
+        live = open(REF_CLIENT).read()
+        assert client_go_facts(live, old_s) == facts
+        _check_patched_client(_apply_hunk(live, hunk))
 
 
 def test_plain_c_consumer_builds_and_agrees_with_oracle(lib, tmp_path):

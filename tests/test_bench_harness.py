@@ -42,6 +42,43 @@ def test_steady_state_skips_the_fill():
     assert harness.steady_state(0.0, done[:12], 12, 1) is None
 
 
+def test_dump_outputs_exact_within_budget_and_repeatable(tmp_path):
+    from benchkit.common import DUMP_BUDGET, dump_outputs
+    segs = np.zeros(5, dtype=_lib.segment_dtype())
+    segs["offset"] = np.arange(5, dtype=np.uint64) << np.uint64(40)
+    segs["size"], segs["file"], segs["flags"] = 7, np.arange(5), 2
+    segs["hash"] = np.arange(160, dtype=np.uint8).reshape(5, 32)
+    begin = np.array([0, 2, 5], dtype=np.uint64)
+    done = dump_outputs(str(tmp_path / "a"), {"segments": segs, "file_begin": begin})
+    got = np.load(tmp_path / "a" / "segments.npy")
+    assert got.dtype == np.float64 and got.shape == (5, 36) and done["segments"]["rows"] == 5
+    assert np.array_equal(got[:, 0].astype(np.uint64), segs["offset"])
+    assert np.array_equal(got[:, 1:4], np.stack([segs["size"], segs["file"], segs["flags"]], 1))
+    assert np.array_equal(got[:, 4:].astype(np.uint8), segs["hash"])
+    assert np.array_equal(np.load(tmp_path / "a" / "file_begin.npy"), begin.astype(np.float64))
+    # larger than its share of the budget: the same sample of rows, in order, every time
+    big = np.zeros(DUMP_BUDGET // 2 // (36 * 8) + 1000, dtype=_lib.segment_dtype())
+    big["file"] = np.arange(len(big))
+    for d in ("b", "c"):
+        done = dump_outputs(str(tmp_path / d), {"segments": big, "file_begin": begin})
+    b, c = np.load(tmp_path / "b" / "segments.npy"), np.load(tmp_path / "c" / "segments.npy")
+    assert np.array_equal(b, c) and done["segments"]["of"] == len(big)
+    assert len(b) < len(big) and np.all(np.diff(b[:, 2]) > 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 64 << 20
+
+
+def test_side_legs_are_behind_full(monkeypatch):
+    import sys
+
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs == "" and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
 def _args(**kw):
     a = dict(config="c2", files=4, file_bytes=3 << 20, group=2, seed=-1, mem_threshold=10 ** 9,
              dedup="blocks", path="put")

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 o=gpurun_out/${1:-uwab}
 mkdir -p $o
-B="--path uw --config c4 --uw-bytes 34359738368 --steps 2 --warmup 1 --no-cpu-baseline"
+B="--full --path uw --config c4 --uw-bytes 34359738368 --steps 2 --warmup 1 --no-cpu-baseline"
 run() { name=$1; shift; timeout -k 10 240 python bench.py $B "$@" > $o/$name.json 2> $o/$name.err && \
   python -c "import json,sys; d=json.load(open('$o/$name.json')); print('$name', d['value'], d['ms_per_step'], d['commit_filesets_digest'], d['stages_ms'])"; }
 run default &&
