@@ -156,6 +156,43 @@ int pfscdc_get_chunks(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes, int c
 /* Device time (ms) of the last pfscdc_get_chunks kernels (after the input copy). */
 int pfscdc_last_get_ms(pfscdc_ctx* ctx, float* ms);
 
+/* One DataRef's bytes inside a batch of stored chunks: bytes [offset, offset + size) of the
+ * plaintext of chunk `chunk` (DataRef.OffsetBytes / SizeBytes, chunk.proto). */
+typedef struct pfscdc_slice {
+  uint32_t chunk;    /* index into chunk_offsets / refs */
+  uint32_t reserved;
+  uint64_t offset;   /* DataRef.OffsetBytes */
+  uint64_t size;     /* DataRef.SizeBytes (0 is legal and writes nothing) */
+} pfscdc_slice;      /* 24 bytes */
+
+/* chunk.Reader.Get (reader.go:43-48; per DataRef DataReader.Get, reader.go:72-79) over a
+ * batch of stored chunks (ctext, chunk_offsets, refs as for pfscdc_get_chunks): out receives,
+ * back to back in slice order, the plaintext bytes [offset, offset + size) of each slice's
+ * chunk.  Slices may name chunks in any order, repeat and overlap.  Every chunk that a slice
+ * names is verified once
+ * (BLAKE2b-256 of the stored bytes against refs[c].id, verifyData, transform.go:207-215) unless
+ * verified[c] != 0 (verified NULL = verify all): a chunk the caller has verified before counts
+ * as ok and is not hashed again, the memCache hit of chunk.Get (transform.go:50-53).  ChaCha20
+ * is seekable (RFC 8439 §2.4, zero nonce, block counter = offset / 64, transform.go:159-170), so
+ * only the 64-byte keystream blocks that a slice touches are computed and only the slices'
+ * bytes are read and written: a 4 KiB file packed into an 8 MB chunk costs 4 KiB of decryption.
+ * chunk_ok[c] (nchunks entries): 1 iff chunk c was verified now or marked verified; a chunk no
+ * slice names is not hashed and reports its verified mark.  slice_ok (nullable, nslices
+ * entries) = chunk_ok of the slice's chunk.  The bytes of a slice whose chunk is not ok are
+ * zeros: nothing decrypted from unverified ciphertext reaches out.
+ * ctext: device pointer (16-B aligned) if ctext_on_device, else host memory.  out: device
+ * pointer if out_on_device, else host memory, of sum(size) bytes at any alignment; when both are
+ * device pointers they must not overlap.  PFSCDC_EINVAL for a slice with chunk >= nchunks or
+ * offset + size beyond its chunk.  Returns PFSCDC_OK even when some chunk fails verification
+ * (see chunk_ok).  Synchronous on the ctx stream (ordering: pfscdc_stream_wait). */
+int pfscdc_read_slices(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes, int ctext_on_device,
+                       const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
+                       const uint8_t* verified, const pfscdc_slice* slices, uint32_t nslices,
+                       void* out, int out_on_device, uint8_t* chunk_ok, uint8_t* slice_ok);
+/* Device time (ms) of the last pfscdc_read_slices / pfscdc_store_read: out[0] verification (the
+ * hash pass and the id compare), out[1] the sliced decrypt-and-gather kernel. */
+int pfscdc_last_read_timings(pfscdc_ctx* ctx, float out[2]);
+
 /* chunk.Create(ctx, CreateOptions{}, chunk, createFunc) (transform.go:26-46) for a batch of
  * formed chunks, the upload half of processChunk (writer.go:233-271): chunk i is bytes
  * [chunk_offsets[i], chunk_offsets[i+1]) (offsets as for pfscdc_get_chunks).  refs[i] gets
@@ -338,6 +375,17 @@ int pfscdc_store_put(pfscdc_store* s, const uint8_t id[32], const void* ctext, u
 int pfscdc_store_get(const pfscdc_store* s, const uint8_t id[32], const void** ctext,
                      uint64_t* n);
 uint64_t pfscdc_store_count(const pfscdc_store* s);
+/* chunk.Storage.NewReader(ctx, dataRefs).Get(w) (storage.go:50-55, reader.go:43-48) against a
+ * store, the call under every GetFile: out receives the concatenation of the n DataRefs' bytes
+ * (*nwritten of them, nullable).  The distinct chunks of drs (by Ref.Id) are uploaded once and
+ * verified once each, however many DataRefs share them, then gathered by pfscdc_read_slices'
+ * kernel.  out: device pointer if out_on_device, else host memory, out_cap bytes.
+ * PFSCDC_ENOTFOUND: a Ref.Id is not in the store.  PFSCDC_ECORRUPT: a chunk fails verification
+ * or its stored length differs from ref_size; nothing is then written to out.  PFSCDC_EINVAL: a
+ * DataRef reaching past its ref_size, or out_cap below the DataRefs' total size. */
+int pfscdc_store_read(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_full_dataref* drs,
+                      uint32_t n, void* out, uint64_t out_cap, int out_on_device,
+                      uint64_t* nwritten);
 
 /* batch_bytes: flush threshold for buffered file bytes (0 = 1 GiB).  If ctx has
  * PFSCDC_OPT_REF_IDS set when the writer is created, every chunk also gets its Ref

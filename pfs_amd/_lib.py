@@ -20,6 +20,8 @@ PFSCDC_ENOMEM = -3
 PFSCDC_EUNSUPPORTED = -4
 PFSCDC_ESTATE = -5
 PFSCDC_ECALLBACK = -6
+PFSCDC_ECORRUPT = -7
+PFSCDC_ENOTFOUND = -8
 
 SEG_VALID = 1
 SEG_CUT = 2
@@ -60,6 +62,7 @@ EXPORTED = [
     "pfscdc_group_file_segment_begin", "pfscdc_group_refs", "pfscdc_group_part_begin",
     "pfscdc_group_index_device", "pfscdc_group_last_timings", "pfscdc_uw_create_group",
     "pfscdc_group_scan_stream",
+    "pfscdc_read_slices", "pfscdc_last_read_timings", "pfscdc_store_read",
 ]
 
 
@@ -118,9 +121,20 @@ assert C.sizeof(Segment) == 56 and C.sizeof(Params) == 32 and C.sizeof(ChunkRef)
 WRITER_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(ChunkRef), C.POINTER(AnnotationOut),
                         C.c_uint32)
 
-# numpy views of pfscdc_segment / pfscdc_ref
+# numpy views of pfscdc_segment / pfscdc_ref / pfscdc_slice
 SEGMENT_DTYPE = None
 REF_DTYPE = None
+SLICE_DTYPE = None
+
+
+def slice_dtype():
+    global SLICE_DTYPE
+    if SLICE_DTYPE is None:
+        import numpy as np
+        SLICE_DTYPE = np.dtype([("chunk", "<u4"), ("reserved", "<u4"), ("offset", "<u8"),
+                                ("size", "<u8")])
+        assert SLICE_DTYPE.itemsize == 24
+    return SLICE_DTYPE
 
 
 def ref_dtype():
@@ -262,6 +276,10 @@ def load() -> C.CDLL:
             "pfscdc_group_last_timings": (i32, [vp, P(C.c_float), P(C.c_float), P(u64)]),
             "pfscdc_uw_create_group": (i32, [vp, i64, P(Params), UW_CB, vp, P(vp)]),
             "pfscdc_group_scan_stream": (i32, [vp, vp, u64]),
+            "pfscdc_read_slices": (i32, [vp, vp, u64, i32, P(u64), u32, vp, vp, vp, u32, vp, i32,
+                                         vp, vp]),
+            "pfscdc_last_read_timings": (i32, [vp, P(C.c_float)]),
+            "pfscdc_store_read": (i32, [vp, vp, P(FullDataRef), u32, vp, u64, i32, P(u64)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

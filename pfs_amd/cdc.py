@@ -229,6 +229,74 @@ class Chunker:
         self._check(rc, "get_chunks")
         return res, ok[:n].astype(bool)
 
+    def read_slices(self, ctext, chunk_offsets: Sequence[int], refs: np.ndarray, slices,
+                    out=None, verified=None):
+        """chunk.Reader.Get over a batch of stored chunks (pfscdc_read_slices): the
+        concatenation of plaintext[offset:offset + size] of each slice's chunk.  ``slices``:
+        (chunk, offset, size) triples or a SLICE_DTYPE array; ``ctext``: host bytes/array or a
+        torch uint8 CUDA tensor; ``out``: optional contiguous torch uint8 tensor (CUDA or CPU)
+        or numpy uint8 array of at least the slices' total size, at any alignment;
+        ``verified``: per-chunk marks of chunks verified before (not hashed again).  Returns
+        (plaintext, chunk_ok[nchunks], slice_ok[nslices]); the bytes of a slice whose chunk is
+        not ok are zeros."""
+        offs = _offsets_array(chunk_offsets)
+        n = len(offs) - 1
+        refs = np.ascontiguousarray(refs, dtype=_lib.ref_dtype())
+        if len(refs) != n:
+            raise ValueError("one ref per chunk")
+        sdt = _lib.slice_dtype()
+        if isinstance(slices, np.ndarray) and slices.dtype == sdt:
+            sl = np.ascontiguousarray(slices)
+        else:
+            sl = np.zeros(len(slices), dtype=sdt)
+            for i, (ch, o, z) in enumerate(slices):
+                sl[i] = (ch, 0, o, z)
+        ns = len(sl)
+        total = int(sl["size"].sum()) if ns else 0
+        ver = None
+        if verified is not None:
+            ver = np.ascontiguousarray(np.asarray(verified).astype(np.uint8))
+            if len(ver) != n:
+                raise ValueError("one verified mark per chunk")
+        self._after_torch(ctext, out)
+        if hasattr(ctext, "is_cuda") and ctext.is_cuda:
+            if ctext.dtype.itemsize != 1 or not ctext.is_contiguous():
+                raise ValueError("device ctext must be a contiguous uint8 tensor")
+            cptr, nbytes, con = ctext.data_ptr(), ctext.numel(), 1
+        else:
+            arr = np.ascontiguousarray(np.frombuffer(ctext, dtype=np.uint8)
+                                       if isinstance(ctext, (bytes, bytearray)) else ctext,
+                                       dtype=np.uint8)
+            cptr, nbytes, con = (arr.ctypes.data if arr.size else None), arr.size, 0
+            self._get_keep = arr
+        if out is None:
+            res = np.empty(total, dtype=np.uint8)
+            optr, oon = (res.ctypes.data if total else None), 0
+        elif isinstance(out, np.ndarray):
+            if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < total:
+                raise ValueError("out must be a contiguous uint8 array of the slices' size")
+            res, optr, oon = out, (out.ctypes.data if out.size else None), 0
+        else:
+            if out.dtype.itemsize != 1 or not out.is_contiguous() or out.numel() < total:
+                raise ValueError("out must be a contiguous uint8 tensor of the slices' size")
+            res, optr, oon = out, (out.data_ptr() if out.numel() else None), int(out.is_cuda)
+        cok = np.zeros(max(n, 1), dtype=np.uint8)
+        sok = np.zeros(max(ns, 1), dtype=np.uint8)
+        rc = self.lib.pfscdc_read_slices(self.ctx, cptr, nbytes, con,
+                                         offs.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                         refs.ctypes.data if n else None,
+                                         ver.ctypes.data if ver is not None and n else None,
+                                         sl.ctypes.data if ns else None, ns, optr, oon,
+                                         cok.ctypes.data, sok.ctypes.data)
+        self._check(rc, "read_slices")
+        return res, cok[:n].astype(bool), sok[:ns].astype(bool)
+
+    def last_read_timings(self) -> dict:
+        """Device ms of the last read_slices / store read: verification and the gather."""
+        out = (C.c_float * 2)()
+        self._check(self.lib.pfscdc_last_read_timings(self.ctx, out), "read_timings")
+        return {"verify": out[0], "gather": out[1]}
+
     def form_chunks(self, stream_file_begin: Optional[Sequence[int]] = None):
         """Chunks chunk.Writer forms over the last scan's files (pfscdc_form_chunks), each
         stream (files [b[k], b[k+1])) one writer.  Returns (chunk_offsets uint64[n+1],

@@ -3,6 +3,8 @@
 Reference interface (paths under /root/reference/src/internal/storage/chunk):
 
 * ``Storage.NewWriter(ctx, name, cb, ...WriterOption) *Writer``   storage.go:60-66
+* ``Storage.NewReader(ctx, dataRefs) *Reader``, ``Reader.Iterate / Get`` storage.go:50-55,
+  reader.go:30-48
 * ``Writer.Annotate / Write / Close / ChunkCount / AnnotationCount`` writer.go:105-143,423
 * ``WriterCallback func([]*Annotation) error``                      writer.go:31
 * ``WithRollingHashConfig(averageBits, seed)``, ``WithMinMax(min, max)``,
@@ -160,6 +162,87 @@ class Storage:
         for o in opts:
             o(cfg)
         return Writer(cfg, cb, self.device, self.batch_bytes, self.store)
+
+    def new_reader(self, data_refs: list) -> "Reader":
+        """``Storage.NewReader(ctx, dataRefs)`` (storage.go:50-55)."""
+        return Reader(list(data_refs), self.device, self.store)
+
+
+class Reader:
+    """``chunk.Reader`` (reader.go:12-48): reads the bytes a list of DataRefs names from the
+    storage's chunk store.  Each distinct chunk is uploaded and verified once per ``get``,
+    however many DataRefs share it, and only the referenced bytes are decrypted
+    (pfscdc_store_read)."""
+
+    def __init__(self, data_refs: list, device: int, store: Optional[ChunkStore]):
+        self.data_refs = data_refs
+        self.device = device
+        self._store = store
+
+    def iterate(self, cb: Callable[[DataRef], None]) -> None:
+        """``Reader.Iterate`` (reader.go:30-41): ``cb`` gets the DataRefs one by one."""
+        for dr in self.data_refs:
+            cb(dr)
+
+    def size(self) -> int:
+        return sum(dr.size_bytes for dr in self.data_refs)
+
+    def _validate(self) -> None:
+        if self._store is None:
+            raise ValueError("the storage has no chunk store to read from")
+        for i, dr in enumerate(self.data_refs):
+            if dr.offset_bytes < 0 or dr.size_bytes < 0 or \
+                    dr.offset_bytes + dr.size_bytes > dr.ref.size_bytes:
+                raise ValueError(f"DataRef {i} reaches past its chunk: offset {dr.offset_bytes} "
+                                 f"+ size {dr.size_bytes} > Ref.size_bytes {dr.ref.size_bytes}")
+
+    def _read(self, ptr, cap: int, on_device: int) -> int:
+        from .cdc import Chunker
+
+        n = len(self.data_refs)
+        arr = (_lib.FullDataRef * max(1, n))()
+        for i, d in enumerate(self.data_refs):
+            arr[i] = _full(d)
+        c = Chunker(ChunkParams(), self.device)
+        try:
+            nw = C.c_uint64()
+            rc = c.lib.pfscdc_store_read(c.ctx, self._store._s, arr, n, ptr, cap, on_device,
+                                         C.byref(nw))
+            msg = c.lib.pfscdc_last_error(c.ctx)
+        finally:
+            c.close()
+        if rc == _lib.PFSCDC_ENOTFOUND:
+            for d in self.data_refs:
+                self._store.get(d.ref.id)  # raises KeyError for the missing id
+            raise KeyError("chunk not in the store")
+        if rc:
+            raise _lib.PfsCdcError(rc, f"Reader.Get: {msg.decode() if msg else ''}")
+        return nw.value
+
+    def get(self) -> bytes:
+        """``Reader.Get`` (reader.go:43-48): the concatenation of the DataRefs' bytes.
+        ValueError for a DataRef reaching past its chunk, KeyError for a chunk missing from
+        the store, PfsCdcError (PFSCDC_ECORRUPT) for a chunk that fails verification."""
+        self._validate()
+        total = self.size()
+        buf = (C.c_uint8 * max(1, total))()
+        n = self._read(buf, total, 0)
+        return bytes(memoryview(buf)[:n])
+
+    def get_into(self, tensor) -> int:
+        """``Reader.Get`` into a contiguous torch uint8 tensor (CUDA: the bytes stay on the
+        device); returns the number of bytes written.  Nothing is written on an error."""
+        self._validate()
+        if tensor.dtype.itemsize != 1 or not tensor.is_contiguous():
+            raise ValueError("get_into needs a contiguous uint8 tensor")
+        if tensor.numel() < self.size():
+            raise ValueError("tensor smaller than the DataRefs' total size")
+        if tensor.is_cuda:
+            import torch
+
+            torch.cuda.current_stream(tensor.device).synchronize()  # earlier writes have landed
+        return self._read(tensor.data_ptr() if tensor.numel() else None, tensor.numel(),
+                          int(tensor.is_cuda))
 
 
 class Writer:

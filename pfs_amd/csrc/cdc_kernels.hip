@@ -1935,6 +1935,142 @@ __global__ __launch_bounds__(kChachaBlock) void chacha_xor_coalesced_kernel(
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
 }
+
+// 5e. chunk.Reader.Get (reader.go:43-79): the concatenation of chunk[offset, offset + size) over
+// a list of slices of stored chunks, decrypted (transform.go:159-170).  ChaCha20 is seekable, so
+// only the keystream blocks a slice touches are computed: slice i covers blocks offset / 64 ..
+// (offset + size - 1) / 64 of its chunk, blk_base[i] is the prefix sum of those counts over the
+// (non-empty) slices, and consecutive lanes take consecutive blocks of that list, so a wave's 64
+// blocks map to one contiguous range of out.  As in the kernel above a lane parks its block's
+// keystream in LDS (same slot rotation) and the wave then walks the window as 256 pieces of 16
+// keystream bytes.  A piece lies at an arbitrary byte address on both sides (a chunk starts
+// anywhere in ctext, a slice anywhere in its chunk and in out): whole pieces move as one
+// unaligned 16-byte load and store; the pieces cut by a slice's first or last byte move byte by
+// byte, so no byte outside [out_off[i], out_off[i] + size) is written (the neighbouring slice's
+// bytes are another lane's) and no byte outside the slice is read.  A slice of a chunk whose ok
+// flag is 0 reads no ciphertext and computes no keystream: its bytes are zeros.
+__global__ __launch_bounds__(kChachaBlock) void chacha_slice_gather_kernel(
+    const uint8_t* __restrict__ ctext, const uint64_t* __restrict__ chunk_offs,
+    const pfscdc_ref* __restrict__ refs, const uint8_t* __restrict__ ok,
+    const pfscdc_slice* __restrict__ slices, const uint64_t* __restrict__ out_off,
+    const uint64_t* __restrict__ blk_base, uint32_t n, uint8_t* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_ks[kChachaBlock / 64][64 * 16];
+  __shared__ uint64_t s_src[kChachaBlock / 64][64];  // ctext index of the block's keystream byte 0
+  __shared__ uint64_t s_dst[kChachaBlock / 64][64];  // index in out of the same byte (mod 2^64)
+  __shared__ uint32_t s_rng[kChachaBlock / 64][64];  // first | last << 8 | ok << 16 (0: no block)
+  const uint64_t nblocks = blk_base[n];
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = threadIdx.x >> 6;
+  uint32_t* const ks = s_ks[wv];
+  const uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x +
+                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
+  for (uint64_t g0 = w0; g0 < nblocks; g0 += stride) {
+    uint32_t lo = 0, hi = n;  // the last r with blk_base[r] <= g0
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (blk_base[mid] <= g0) lo = mid;
+      else hi = mid;
+    }
+    const uint64_t g = g0 + lane;
+    uint32_t x[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) x[i] = 0;
+    uint64_t src = 0, dst = 0;
+    uint32_t rng = 0;
+    if (g < nblocks) {
+      while (blk_base[lo + 1] <= g) lo++;
+      const pfscdc_slice sl = slices[lo];
+      const uint64_t blk = sl.offset / 64 + (g - blk_base[lo]);  // keystream block of the chunk
+      const uint64_t b0 = 64 * blk, end = sl.offset + sl.size;
+      // the slice's bytes of this block: keystream bytes [first, last)
+      const uint32_t first = b0 < sl.offset ? (uint32_t)(sl.offset - b0) : 0u;
+      const uint32_t last = end - b0 >= 64 ? 64u : (uint32_t)(end - b0);
+      const uint32_t good = ok[sl.chunk] ? 1u : 0u;
+      src = chunk_offs[sl.chunk] + b0;
+      dst = out_off[lo] + b0 - sl.offset;  // below zero (mod 2^64) by `first` in a head block
+      rng = first | last << 8 | good << 16;
+      if (good) {
+        const uint4 k0 = reinterpret_cast<const uint4*>(refs[sl.chunk].dek)[0];
+        const uint4 k1 = reinterpret_cast<const uint4*>(refs[sl.chunk].dek)[1];
+        const uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u,
+                                k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w,
+                                (uint32_t)blk, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < 16; i++) x[i] = s[i];
+#pragma unroll
+        for (int r = 0; r < 10; r++) {
+          PFS_CQR(0, 4, 8, 12);
+          PFS_CQR(1, 5, 9, 13);
+          PFS_CQR(2, 6, 10, 14);
+          PFS_CQR(3, 7, 11, 15);
+          PFS_CQR(0, 5, 10, 15);
+          PFS_CQR(1, 6, 11, 12);
+          PFS_CQR(2, 7, 8, 13);
+          PFS_CQR(3, 4, 9, 14);
+        }
+#pragma unroll
+        for (int i = 0; i < 16; i++) x[i] += s[i];
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const uint32_t slot = ((uint32_t)q + (lane >> 1)) & 3u;
+      *reinterpret_cast<uint4*>(ks + lane * 16 + 4 * slot) =
+          make_uint4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+    }
+    s_src[wv][lane] = src;
+    s_dst[wv][lane] = dst;
+    s_rng[wv][lane] = rng;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // piece p = lane + 64 i is keystream bytes [16 q, 16 q + 16) of block j = p >> 2, q = p & 3
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t p = lane + 64u * (uint32_t)i, j = p >> 2, q = p & 3u;
+      const uint32_t r = s_rng[wv][j];
+      const uint32_t a = max(r & 0xffu, 16u * q), b = min((r >> 8) & 0xffu, 16u * q + 16u);
+      if (a >= b) continue;
+      const bool good = (r >> 16) != 0;
+      const uint32_t* kp = ks + j * 16 + 4 * ((q + (j >> 1)) & 3u);
+      const uint64_t sj = s_src[wv][j], dj = s_dst[wv][j];
+      if (b - a == 16) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (good) {
+          const uint4 k = *reinterpret_cast<const uint4*>(kp);
+          __builtin_memcpy(&v, ctext + (sj + a), 16);
+          v.x ^= k.x;
+          v.y ^= k.y;
+          v.z ^= k.z;
+          v.w ^= k.w;
+        }
+        __builtin_memcpy(out + (dj + a), &v, 16);
+      } else {  // a slice's first or last bytes: only its own
+        const uint8_t* kb = reinterpret_cast<const uint8_t*>(kp);
+        for (uint32_t t = a; t < b; t++)
+          out[dj + t] = good ? (uint8_t)(ctext[sj + t] ^ kb[t & 15u]) : (uint8_t)0;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();  // the window's keystream is read before the next one lands
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
+
+// verifyData (transform.go:207-215) for the read path: record i of a kModeHash pass over stored
+// chunks (file = chunk index) carries BLAKE2b-256 of the stored bytes; ok[chunk] = 1 iff it is
+// the chunk's Ref.Id.
+__global__ void verify_ids_kernel(const pfscdc_segment* __restrict__ segs, uint32_t n,
+                                  const pfscdc_ref* __restrict__ refs, uint8_t* __restrict__ ok) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t c = segs[i].file;
+  const uint64_t* h = reinterpret_cast<const uint64_t*>(segs[i].hash);
+  const uint64_t* id = reinterpret_cast<const uint64_t*>(refs[c].id);
+  ok[c] = (h[0] == id[0] && h[1] == id[1] && h[2] == id[2] && h[3] == id[3]) ? 1 : 0;
+}
 #undef PFS_CQR
 
 // 5c. BLAKE2b-256, one lane per segment.  No cross-lane traffic at all: the 16-word state,
@@ -2249,6 +2385,25 @@ hipError_t launch_get(const uint8_t* ctext, const uint64_t* offs, pfscdc_segment
   blake2b_kernel<kModeGet><<<hash_grid(nsegs, num_cus, waves), kHashBlock, 0, st>>>(
       ctext, offs, segs, seg_count, order, counter, nbytes, refs, ptext, prio_arg(0), nullptr,
       nullptr, nullptr, 0u);
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_ids(const pfscdc_segment* segs, uint32_t n, const pfscdc_ref* refs,
+                             uint8_t* ok, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  verify_ids_kernel<<<(n + 255) / 256, 256, 0, st>>>(segs, n, refs, ok);
+  return hipGetLastError();
+}
+
+hipError_t launch_slice_gather(const uint8_t* ctext, const uint64_t* chunk_offs,
+                               const pfscdc_ref* refs, const uint8_t* ok,
+                               const pfscdc_slice* slices, const uint64_t* out_off,
+                               const uint64_t* blk_base, uint32_t n, uint64_t nblocks,
+                               uint8_t* out, int num_cus, hipStream_t st) {
+  if (nblocks == 0) return hipSuccess;
+  const uint64_t need = (nblocks + kChachaBlock - 1) / kChachaBlock, full = (uint64_t)num_cus * 32;
+  chacha_slice_gather_kernel<<<(unsigned)(need < full ? need : full), kChachaBlock, 0, st>>>(
+      ctext, chunk_offs, refs, ok, slices, out_off, blk_base, n, out);
   return hipGetLastError();
 }
 

@@ -119,6 +119,15 @@ struct pfscdc_ctx {
   PinnedBuf<uint64_t> h_blk;
   PinnedBuf<pfscdc_segment> h_segs2;
   PinnedBuf<pfscdc_ref> h_refs;
+  // read_slices: the non-empty slices, {out_off[m + 1], blk_base[m + 1]}, per-chunk ok flags
+  DevBuf<pfscdc_slice> d_rslices;
+  DevBuf<uint64_t> d_rmeta;
+  DevBuf<uint8_t> d_rok;
+  PinnedBuf<pfscdc_slice> h_rslices;
+  PinnedBuf<uint64_t> h_rmeta;
+  PinnedBuf<uint8_t> h_rok;
+  hipEvent_t rev[3] = {nullptr, nullptr, nullptr};  // before the verification, the gather, after
+  float read_ms[2] = {0.f, 0.f};
   uint32_t options = 0;
   float get_ms = 0.f;
   float create_ms = 0.f, create_hash_ms = 0.f;
@@ -362,6 +371,14 @@ int pfscdc_ctx_destroy(pfscdc_ctx* c) {
   c->h_seg_base.release();
   c->h_seg_begin.release();
   c->h_segs.release();
+  c->d_rslices.release();
+  c->d_rmeta.release();
+  c->d_rok.release();
+  c->h_rslices.release();
+  c->h_rmeta.release();
+  c->h_rok.release();
+  for (auto& e : c->rev)
+    if (e) (void)hipEventDestroy(e);
   if (c->d_table) (void)hipFree(c->d_table);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
@@ -1378,6 +1395,22 @@ int pfscdc_last_get_ms(pfscdc_ctx* c, float* ms) {
   return PFSCDC_OK;
 }
 
+int pfscdc_read_slices(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctext_on_device,
+                       const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
+                       const uint8_t* verified, const pfscdc_slice* slices, uint32_t nslices,
+                       void* out, int out_on_device, uint8_t* chunk_ok, uint8_t* slice_ok) {
+  return read_slices_impl(c, ctext, nbytes, ctext_on_device, chunk_offsets, nchunks, refs,
+                          verified, slices, nslices, out, out_on_device, chunk_ok, slice_ok,
+                          false);
+}
+
+int pfscdc_last_read_timings(pfscdc_ctx* c, float out[2]) {
+  if (!c || !out) return PFSCDC_EINVAL;
+  out[0] = c->read_ms[0];
+  out[1] = c->read_ms[1];
+  return PFSCDC_OK;
+}
+
 void* pfscdc_host_alloc(uint64_t nbytes) {
   void* p = nullptr;
   if (hipHostMalloc(&p, nbytes ? nbytes : 1, hipHostMallocDefault) != hipSuccess) return nullptr;
@@ -1512,6 +1545,173 @@ int hash_records_device(pfscdc_ctx* c, const uint8_t* data, uint64_t nbytes,
   for (uint32_t i = 0; i < n; i++) std::memcpy(out + 32ull * i, c->h_segs.p[i].hash, 32);
   c->nsegs = 0;
   c->have_refs = false;
+  return PFSCDC_OK;
+}
+
+// chunk.Reader.Get over a batch of stored chunks (reader.go:43-79).  Two passes on the ctx
+// stream: verifyData (transform.go:207-215) as one kModeHash launch over the stored bytes of
+// the chunks that a slice names and the caller has not verified before (the memCache miss,
+// transform.go:50-53), with a compare against Ref.Id that leaves per-chunk ok flags on the
+// device; then the sliced ChaCha20 gather (chacha_slice_gather_kernel) over the non-empty
+// slices.  strict (pfscdc_store_read): the flags are fetched between the passes and a bad chunk
+// ends the call before the gather.
+int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctext_on_device,
+                     const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
+                     const uint8_t* verified, const pfscdc_slice* slices, uint32_t nslices,
+                     void* out, int out_on_device, uint8_t* chunk_ok, uint8_t* slice_ok,
+                     bool strict) {
+  if (!c) return PFSCDC_EINVAL;
+  if (c->pending) return fail(c, PFSCDC_ESTATE, "read_slices during a pending scan");
+  if (!chunk_offsets || (nchunks && (!refs || !chunk_ok)) || (nbytes && !ctext) ||
+      (nslices && !slices))
+    return fail(c, PFSCDC_EINVAL, "NULL argument");
+  if (chunk_offsets[0] != 0 || chunk_offsets[nchunks] != nbytes)
+    return fail(c, PFSCDC_EINVAL, "chunk_offsets must start at 0 and end at nbytes");
+  for (uint32_t i = 0; i < nchunks; i++)
+    if (chunk_offsets[i + 1] < chunk_offsets[i])
+      return fail(c, PFSCDC_EINVAL, "chunk_offsets must be nondecreasing");
+  if (ctext_on_device && ((uintptr_t)ctext & 15))
+    return fail(c, PFSCDC_EINVAL, "device ctext must be 16-byte aligned");
+  uint64_t total = 0, nblocks = 0;
+  uint32_t m = 0;  // non-empty slices
+  for (uint32_t i = 0; i < nslices; i++) {
+    const pfscdc_slice& s = slices[i];
+    if (s.chunk >= nchunks) return fail(c, PFSCDC_EINVAL, "slice names a chunk >= nchunks");
+    const uint64_t csize = chunk_offsets[s.chunk + 1] - chunk_offsets[s.chunk];
+    if (s.offset > csize || s.size > csize - s.offset)
+      return fail(c, PFSCDC_EINVAL, "slice reaches past the end of its chunk");
+    if (!s.size) continue;
+    if (total + s.size < total) return fail(c, PFSCDC_EINVAL, "slice sizes overflow");
+    total += s.size;
+    nblocks += (s.offset + s.size - 1) / 64 - s.offset / 64 + 1;
+    m++;
+  }
+  if (total && !out) return fail(c, PFSCDC_EINVAL, "NULL argument");
+  if (ctext_on_device && out_on_device && total && nbytes) {
+    const uintptr_t a = (uintptr_t)ctext, b = (uintptr_t)out;
+    if (a < b + total && b < a + nbytes)
+      return fail(c, PFSCDC_EINVAL, "out overlaps ctext");
+  }
+  if (nchunks == 0) return PFSCDC_OK;
+  c->scan_valid = false;
+  c->nsegs = 0;  // the staging below overwrites the last scan's records
+  c->have_refs = false;
+  HIP_OK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  for (auto& e : c->rev)
+    if (!e) HIP_OK(c, hipEventCreate(&e));
+  // the ok flags start as the caller's marks; the hash records are the chunks left to verify
+  HIP_OK(c, c->h_rok.ensure(nchunks));
+  for (uint32_t i = 0; i < nchunks; i++) c->h_rok.p[i] = 2;  // 2: no slice names it (yet)
+  for (uint32_t i = 0; i < nslices; i++) c->h_rok.p[slices[i].chunk] = 0;
+  HIP_OK(c, c->h_segs.ensure(nchunks));
+  uint32_t nh = 0;
+  uint64_t longest = 0, sum = 0;
+  for (uint32_t i = 0; i < nchunks; i++) {
+    const bool named = c->h_rok.p[i] == 0;
+    c->h_rok.p[i] = verified && verified[i] ? 1 : 0;
+    if (!named || c->h_rok.p[i]) continue;
+    pfscdc_segment& sg = c->h_segs.p[nh++];
+    std::memset(&sg, 0, sizeof sg);
+    sg.size = chunk_offsets[i + 1] - chunk_offsets[i];
+    sg.file = i;
+    sg.flags = PFSCDC_SEG_VALID;
+    longest = std::max(longest, sg.size);
+    sum += sg.size;
+  }
+  HIP_OK(c, c->h_offs.ensure(nchunks + 1));
+  std::memcpy(c->h_offs.p, chunk_offsets, sizeof(uint64_t) * (nchunks + 1));
+  HIP_OK(c, c->h_refs.ensure(nchunks));
+  std::memcpy(c->h_refs.p, refs, sizeof(pfscdc_ref) * nchunks);
+  HIP_OK(c, c->h_seg_begin.ensure(1));
+  c->h_seg_begin.p[0] = nh;
+  HIP_OK(c, c->h_rslices.ensure(m));
+  HIP_OK(c, c->h_rmeta.ensure(2 * ((size_t)m + 1)));
+  uint64_t* const h_out_off = c->h_rmeta.p;
+  uint64_t* const h_blk = c->h_rmeta.p + m + 1;
+  {
+    uint32_t k = 0;
+    uint64_t o = 0, b = 0;
+    for (uint32_t i = 0; i < nslices; i++) {
+      const pfscdc_slice& s = slices[i];
+      if (!s.size) continue;
+      c->h_rslices.p[k] = s;
+      h_out_off[k] = o;
+      h_blk[k] = b;
+      o += s.size;
+      b += (s.offset + s.size - 1) / 64 - s.offset / 64 + 1;
+      k++;
+    }
+    h_out_off[m] = o;
+    h_blk[m] = b;
+  }
+  HIP_OK(c, c->d_offs.ensure(nchunks + 1));
+  HIP_OK(c, c->d_segs.ensure(nchunks));
+  HIP_OK(c, c->d_refs.ensure(nchunks));
+  HIP_OK(c, c->d_order.ensure(nchunks));
+  HIP_OK(c, c->d_qctr.ensure(2));
+  HIP_OK(c, c->d_counts.ensure(4));
+  HIP_OK(c, c->d_rok.ensure(nchunks));
+  HIP_OK(c, c->d_rslices.ensure(m));
+  HIP_OK(c, c->d_rmeta.ensure(2 * ((size_t)m + 1)));
+  const uint8_t* in;
+  if (ctext_on_device) {
+    in = (const uint8_t*)ctext;
+  } else {
+    HIP_OK(c, c->d_data.ensure(nbytes + 64));
+    if (nbytes) HIP_OK(c, hipMemcpyAsync(c->d_data.p, ctext, nbytes, hipMemcpyHostToDevice, st));
+    in = c->d_data.p;
+  }
+  uint8_t* outp;
+  if (out_on_device) {
+    outp = (uint8_t*)out;
+  } else {
+    HIP_OK(c, c->d_out.ensure(total + 64));
+    outp = c->d_out.p;
+  }
+  HIP_OK(c, hipMemcpyAsync(c->d_offs.p, c->h_offs.p, sizeof(uint64_t) * (nchunks + 1),
+                           hipMemcpyHostToDevice, st));
+  HIP_OK(c, hipMemcpyAsync(c->d_refs.p, c->h_refs.p, sizeof(pfscdc_ref) * nchunks,
+                           hipMemcpyHostToDevice, st));
+  HIP_OK(c, hipMemcpyAsync(c->d_rok.p, c->h_rok.p, nchunks, hipMemcpyHostToDevice, st));
+  if (nh)
+    HIP_OK(c, hipMemcpyAsync(c->d_segs.p, c->h_segs.p, sizeof(pfscdc_segment) * nh,
+                             hipMemcpyHostToDevice, st));
+  HIP_OK(c, hipMemcpyAsync(c->d_counts.p + 1, c->h_seg_begin.p, sizeof(uint64_t),
+                           hipMemcpyHostToDevice, st));
+  if (m)
+    HIP_OK(c, hipMemcpyAsync(c->d_rslices.p, c->h_rslices.p, sizeof(pfscdc_slice) * m,
+                             hipMemcpyHostToDevice, st));
+  HIP_OK(c, hipMemcpyAsync(c->d_rmeta.p, c->h_rmeta.p, sizeof(uint64_t) * 2 * ((size_t)m + 1),
+                           hipMemcpyHostToDevice, st));
+  HIP_OK(c, hipEventRecord(c->rev[0], st));
+  HIP_OK(c, launch_blake2b(in, c->d_offs.p, c->d_segs.p, c->d_counts.p + 1, nh, c->d_order.p,
+                           c->d_qctr.p, c->num_cus, nbytes, st, false, nullptr,
+                           knob_waves(longest, sum, c->num_cus)));
+  HIP_OK(c, launch_verify_ids(c->d_segs.p, nh, c->d_refs.p, c->d_rok.p, st));
+  HIP_OK(c, hipMemcpyAsync(c->h_rok.p, c->d_rok.p, nchunks, hipMemcpyDeviceToHost, st));
+  HIP_OK(c, hipEventRecord(c->rev[1], st));
+  if (strict) {
+    HIP_OK(c, hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < nslices; i++)
+      if (!c->h_rok.p[slices[i].chunk]) {
+        std::memcpy(chunk_ok, c->h_rok.p, nchunks);
+        return fail(c, PFSCDC_ECORRUPT, "a stored chunk failed verification");
+      }
+  }
+  HIP_OK(c, launch_slice_gather(in, c->d_offs.p, c->d_refs.p, c->d_rok.p, c->d_rslices.p,
+                                c->d_rmeta.p, c->d_rmeta.p + m + 1, m, nblocks, outp,
+                                c->num_cus, st));
+  HIP_OK(c, hipEventRecord(c->rev[2], st));
+  if (!out_on_device && total)
+    HIP_OK(c, hipMemcpyAsync(out, outp, total, hipMemcpyDeviceToHost, st));
+  HIP_OK(c, hipStreamSynchronize(st));
+  std::memcpy(chunk_ok, c->h_rok.p, nchunks);
+  if (slice_ok)
+    for (uint32_t i = 0; i < nslices; i++) slice_ok[i] = c->h_rok.p[slices[i].chunk];
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, c->rev[0], c->rev[1]) == hipSuccess) c->read_ms[0] = ms;
+  if (hipEventElapsedTime(&ms, c->rev[1], c->rev[2]) == hipSuccess) c->read_ms[1] = ms;
   return PFSCDC_OK;
 }
 

@@ -36,6 +36,7 @@ struct TileRec {
 static_assert(sizeof(TileRec) == 64, "tile record is one 64-byte line");
 static_assert(sizeof(pfscdc_segment) == 56, "segment record layout");
 static_assert(sizeof(pfscdc_ref) == 64, "ref record layout");
+static_assert(sizeof(pfscdc_slice) == 24, "slice record layout");
 
 // Tuning knobs (knobs.cpp): process-wide integers, read from the environment once.
 enum class Knob : int {
@@ -199,6 +200,25 @@ hipError_t launch_get(const uint8_t* ctext, const uint64_t* offs, pfscdc_segment
                       const uint64_t* seg_count, uint64_t nsegs, uint32_t* order, uint32_t* counter,
                       int num_cus, uint64_t nbytes, pfscdc_ref* refs, uint8_t* ptext, hipStream_t st,
                       int waves = 0);
+// the read path (pfscdc_read_slices): ok[segs[i].file] = (segs[i].hash == refs[segs[i].file].id)
+// for the n records of a hash pass over stored chunks
+hipError_t launch_verify_ids(const pfscdc_segment* segs, uint32_t n, const pfscdc_ref* refs,
+                             uint8_t* ok, hipStream_t st);
+// out[out_off[i] + t] = ChaCha20_{refs[c].dek}(chunk c)[offset + t] for the n non-empty slices
+// {c, offset, size} (zeros where ok[c] == 0); blk_base: prefix of the 64-B keystream blocks the
+// slices touch (n + 1 entries, blk_base[n] = nblocks)
+hipError_t launch_slice_gather(const uint8_t* ctext, const uint64_t* chunk_offs,
+                               const pfscdc_ref* refs, const uint8_t* ok,
+                               const pfscdc_slice* slices, const uint64_t* out_off,
+                               const uint64_t* blk_base, uint32_t n, uint64_t nblocks,
+                               uint8_t* out, int num_cus, hipStream_t st);
+// pfscdc_read_slices; strict: PFSCDC_ECORRUPT, before anything is written to out, if a chunk
+// that a slice names fails verification (pfscdc_store_read)
+int read_slices_impl(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes, int ctext_on_device,
+                     const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
+                     const uint8_t* verified, const pfscdc_slice* slices, uint32_t nslices,
+                     void* out, int out_on_device, uint8_t* chunk_ok, uint8_t* slice_ok,
+                     bool strict);
 // segs[i].file += base for i < n (a device group's gathered index: member-local file ids
 // become the commit's)
 hipError_t launch_rebase_files(pfscdc_segment* segs, uint64_t n, uint32_t base, hipStream_t st);

@@ -985,6 +985,56 @@ int pfscdc_store_get(const pfscdc_store* s, const uint8_t id[32], const void** c
 
 uint64_t pfscdc_store_count(const pfscdc_store* s) { return s ? s->objects.size() : 0; }
 
+// Storage.NewReader(dataRefs).Get(w) (storage.go:50-55, reader.go:43-48): the distinct chunks
+// of drs, in order of first use, form one batch of stored chunks; every DataRef is a slice of it.
+int pfscdc_store_read(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_full_dataref* drs,
+                      uint32_t n, void* out, uint64_t out_cap, int out_on_device,
+                      uint64_t* nwritten) {
+  if (!ctx || !s || (n && !drs)) return PFSCDC_EINVAL;
+  if (nwritten) *nwritten = 0;
+  std::map<std::string, uint32_t> index;  // Ref.Id -> chunk of the batch
+  std::vector<const std::string*> objs;
+  std::vector<pfscdc_ref> refs;
+  std::vector<pfscdc_slice> slices(n);
+  uint64_t total = 0;
+  bool corrupt = false;
+  for (uint32_t i = 0; i < n; i++) {
+    const pfscdc_full_dataref& dr = drs[i];
+    if (dr.ref_size < 0 || dr.data.offset_bytes < 0 || dr.data.size_bytes < 0 ||
+        dr.data.offset_bytes > dr.ref_size ||
+        dr.data.size_bytes > dr.ref_size - dr.data.offset_bytes)
+      return PFSCDC_EINVAL;
+    const std::string id((const char*)dr.ref.id, 32);
+    auto it = index.find(id);
+    if (it == index.end()) {
+      auto ob = s->objects.find(id);
+      if (ob == s->objects.end()) return PFSCDC_ENOTFOUND;
+      it = index.emplace(id, (uint32_t)objs.size()).first;
+      objs.push_back(&ob->second);
+      refs.push_back(dr.ref);
+    }
+    // a stored object of another length than Ref.SizeBytes is not the chunk the DataRef names
+    if (objs[it->second]->size() != (uint64_t)dr.ref_size) corrupt = true;
+    slices[i] = pfscdc_slice{it->second, 0, (uint64_t)dr.data.offset_bytes,
+                             (uint64_t)dr.data.size_bytes};
+    total += (uint64_t)dr.data.size_bytes;
+  }
+  if (total > out_cap || (total && !out)) return PFSCDC_EINVAL;
+  if (corrupt) return PFSCDC_ECORRUPT;
+  std::vector<uint64_t> offs(objs.size() + 1, 0);
+  for (size_t k = 0; k < objs.size(); k++) offs[k + 1] = offs[k] + objs[k]->size();
+  std::vector<uint8_t> ct(offs.back());
+  for (size_t k = 0; k < objs.size(); k++)
+    if (!objs[k]->empty()) std::memcpy(ct.data() + offs[k], objs[k]->data(), objs[k]->size());
+  std::vector<uint8_t> ok(objs.size() + 1);
+  int rc = pfscdc::read_slices_impl(ctx, ct.data(), ct.size(), 0, offs.data(),
+                                    (uint32_t)objs.size(), refs.data(), nullptr, slices.data(), n,
+                                    out, out_on_device, ok.data(), nullptr, true);
+  if (rc) return rc;
+  if (nwritten) *nwritten = total;
+  return PFSCDC_OK;
+}
+
 int pfscdc_merge_file_hash(pfscdc_ctx* ctx, pfscdc_store* store, const pfscdc_full_dataref* drs,
                            uint32_t n, uint8_t out[32]) {
   if (!ctx || !store || !out || (n && !drs)) return PFSCDC_EINVAL;

@@ -1,0 +1,133 @@
+"""Read path on one GPU, device-resident: pfscdc_read_slices (chunk.Reader.Get: verify each
+referenced chunk once, decrypt only the referenced bytes) over seeded synthetic chunks that are
+encrypted on the GPU with their own Ref.Dek, as benchkit/get.py does.  Three layouts:
+
+  whole   one DataRef per chunk (the whole chunk), alternated in the same process with
+          pfscdc_get_chunks on the same bytes
+  packed  64 odd-sized slices per chunk, at odd offsets
+  sparse  one 4 KiB slice per chunk, every chunk marked verified (the memCache hit)
+
+Per layout: median device ms of the verification and of the gather kernel after a warm-up, and
+the gather's (bytes read + bytes written) / ms against benchkit.common.HBM_PEAK_GBS, the
+gather kernel's share of HBM peak.  Every output is compared with the plaintext before
+anything is printed.  Writes one JSON (default profiles/r7/read_path/read_bench.json).
+
+usage: python tools/read_bench.py [--chunks N] [--chunk-bytes B] [--reps R] [--warmup W]
+                                  [--out PATH]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from benchkit.common import HBM_PEAK_GBS  # noqa: E402
+from pfs_amd import _lib  # noqa: E402
+from pfs_amd.cdc import ChunkParams, Chunker  # noqa: E402
+
+
+def layouts(nchunks, cb, rng):
+    """name -> (slices, verified, per-chunk (source offset, bytes) of the consecutive run)."""
+    sdt = _lib.slice_dtype()
+    whole = np.zeros(nchunks, dtype=sdt)
+    whole["chunk"] = np.arange(nchunks)
+    whole["size"] = cb
+    per = 64
+    sizes = 2 * rng.integers(0, cb // (2 * per) - 1, (nchunks, per)) + 1  # odd, sum < cb - 1
+    offs = 1 + np.concatenate([np.zeros((nchunks, 1), dtype=np.int64),
+                               np.cumsum(sizes, axis=1)[:, :-1]], axis=1)
+    packed = np.zeros(nchunks * per, dtype=sdt)
+    packed["chunk"] = np.repeat(np.arange(nchunks), per)
+    packed["offset"] = offs.ravel()
+    packed["size"] = sizes.ravel()
+    sparse = np.zeros(nchunks, dtype=sdt)
+    sparse["chunk"] = np.arange(nchunks)
+    sparse["offset"] = rng.integers(0, cb - 4096 + 1, nchunks)
+    sparse["size"] = 4096
+    return {
+        "whole": (whole, None, [(0, cb)] * nchunks),
+        "packed": (packed, None, [(1, int(s)) for s in sizes.sum(axis=1)]),
+        "sparse": (sparse, np.ones(nchunks, dtype=np.uint8),
+                   [(int(o), 4096) for o in sparse["offset"]]),
+    }
+
+
+def check(out, data, cb, runs):
+    """out is the concatenation of data[c * cb + o : ... + n] over the per-chunk runs."""
+    at = 0
+    for c, (o, n) in enumerate(runs):
+        if not torch.equal(out[at:at + n], data[c * cb + o:c * cb + o + n]):
+            raise SystemExit(f"read_bench: output differs from the plaintext in chunk {c}")
+        at += n
+    assert at == out.numel()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--chunks", type=int, default=1024)
+    ap.add_argument("--chunk-bytes", type=int, default=4 << 20)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r7", "read_path",
+                                                  "read_bench.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("read_bench: needs a GPU")
+    n, cb = args.chunks, args.chunk_bytes
+    c = Chunker(ChunkParams(), 0)
+    cofs = np.arange(n + 1, dtype=np.uint64) * np.uint64(cb)
+    data = torch.empty(n * cb, dtype=torch.uint8, device="cuda:0")
+    c.fill_synthetic(data, cofs, 0x7EAD)
+    refs, _ = c.create_refs(data, cofs)  # Ref.Dek and Ref.Id of every chunk
+    ctext = torch.empty_like(data)
+    c.get_chunks(data, cofs, refs, out=ctext)  # XOR is its own inverse: the stored form
+    plain = torch.empty_like(data)
+    rows = []
+    for name, (sl, ver, runs) in layouts(n, cb, np.random.default_rng(7)).items():
+        total = int(sl["size"].sum())
+        out = torch.empty(total, dtype=torch.uint8, device="cuda:0")
+        vms, gms, getms = [], [], []
+        for i in range(args.warmup + args.reps):
+            out.zero_()
+            _, cok, sok = c.read_slices(ctext, cofs, refs, sl, out=out, verified=ver)
+            t = c.last_read_timings()
+            if not (cok.all() and sok.all()):
+                raise SystemExit(f"read_bench: {name}: a chunk failed verification")
+            check(out, data, cb, runs)
+            if name == "whole":  # the same bytes through chunk.Get, alternating
+                _, ok = c.get_chunks(ctext, cofs, refs, out=plain)
+                if not (ok.all() and torch.equal(plain, data)):
+                    raise SystemExit("read_bench: get_chunks output differs from the plaintext")
+                g = c.last_get_ms()
+            if i >= args.warmup:
+                vms.append(t["verify"])
+                gms.append(t["gather"])
+                if name == "whole":
+                    getms.append(g)
+        gm = statistics.median(gms)
+        gbs = 2 * total / (gm * 1e-3) / 1e9
+        row = {"layout": name, "chunks": n, "chunk_bytes": cb, "slices": int(len(sl)),
+               "slice_bytes": total, "verify_ms_median": round(statistics.median(vms), 4),
+               "gather_ms_median": round(gm, 4),
+               "gather_read_plus_written_gbs": round(gbs, 1),
+               "gather_share_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4),
+               "hbm_peak_gbs": HBM_PEAK_GBS, "reps": args.reps, "warmup": args.warmup,
+               "outputs_equal_plaintext": True}
+        if name == "whole":
+            row["get_chunks_ms_median_same_run"] = round(statistics.median(getms), 4)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    c.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump({"tool": "tools/read_bench.py", "device": torch.cuda.get_device_name(0),
+                   "layouts": rows}, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
