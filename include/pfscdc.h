@@ -230,6 +230,10 @@ int pfscdc_hash_data_refs(pfscdc_ctx* ctx, const uint8_t* hashes, uint32_t n, ui
 int pfscdc_last_create_ms(pfscdc_ctx* ctx, float* ms);
 /* Its split: out[0] content-hash pass, out[1] Ref.Id pass (dek, ChaCha20, BLAKE2b). */
 int pfscdc_last_create_timings(pfscdc_ctx* ctx, float out[2]);
+/* The form its Ref.Id pass took on this ctx: *split = 0 fused ChaCha20 + BLAKE2b, 1 a ChaCha20
+ * pass then BLAKE2b of the ciphertext, -1 no batch yet (the library chooses by chunk count,
+ * see the PFSCDC_REFID_SPLIT knob). */
+int pfscdc_last_create_form(pfscdc_ctx* ctx, int* split);
 
 /* ---- one stream split across GPUs (writer.go:163-189 block-parallel) --------
  * A stream of N bytes is cut into equal byte ranges, one per GPU.  The rolling hash at a

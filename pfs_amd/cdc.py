@@ -391,6 +391,14 @@ class Chunker:
         self._check(self.lib.pfscdc_last_create_timings(self.ctx, out), "create_timings")
         return {"content_hash": out[0], "ref_id": out[1]}
 
+    def last_create_split(self) -> Optional[bool]:
+        """Whether the last create_refs / commit_refs on this ctx took the split Ref.Id form
+        (a ChaCha20 pass, then BLAKE2b of the ciphertext) or the fused one
+        (pfscdc_last_create_form); None before any."""
+        v = C.c_int32(-1)
+        self._check(self.lib.pfscdc_last_create_form(self.ctx, C.byref(v)), "create_form")
+        return None if v.value < 0 else bool(v.value)
+
     def last_get_ms(self) -> float:
         ms = C.c_float()
         self._check(self.lib.pfscdc_last_get_ms(self.ctx, C.byref(ms)), "get_ms")

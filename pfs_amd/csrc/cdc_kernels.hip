@@ -2305,12 +2305,24 @@ int hash_waves(uint64_t longest_bytes, uint64_t total_bytes, int num_cus, int fo
   return longest * quads1 >= total ? 1 : kHashWavesPerSimd;
 }
 
+// A launch's workgroups under a PFSCDC_*_GRID knob (0: no cap).  The kernels below take
+// whatever grid they get: quads refill from the queue and the ChaCha20 passes stride over
+// their blocks, and no wave waits for another, so a cap only makes a launch slower.
+static unsigned capped_grid(uint64_t grid, Knob cap_knob) {
+  const int64_t cap = knob(cap_knob);
+  if (cap > 0 && (uint64_t)cap < grid) grid = (uint64_t)cap;
+  return (unsigned)grid;
+}
+
+// Workgroups of a blake2b_kernel launch, any mode: one quad per record up to the device's
+// fill at `waves` per SIMD (the PFSCDC_HASH_GRID knob caps it; waves per SIMD and the
+// fused/split choice are made from the real CU count before this).
 static unsigned hash_grid(uint64_t max_segments, int num_cus, int waves) {
   const uint64_t quads_per_block = kHashBlock / 4;
   const uint64_t need = (max_segments + quads_per_block - 1) / quads_per_block;
   const uint64_t full = (uint64_t)num_cus * 4 * (waves > 0 ? waves : kHashWavesPerSimd) /
                         (kHashBlock / 64);
-  return (unsigned)(need < full ? need : full);
+  return capped_grid(need < full ? need : full, Knob::HashGrid);
 }
 
 hipError_t launch_blake2b(const uint8_t* data, const uint64_t* offs, pfscdc_segment* segs,
@@ -2370,7 +2382,7 @@ hipError_t launch_chacha_xor(const uint8_t* data, const uint64_t* offs, const pf
   // context's launches)
   const uint64_t need = (nblocks + 255) / 256,
                  full = (uint64_t)num_cus * (one_wave_per_simd ? 1 : 32);
-  const unsigned grid = (unsigned)(need < full ? need : full);
+  const unsigned grid = capped_grid(need < full ? need : full, Knob::ChachaGrid);
   chacha_xor_coalesced_kernel<<<grid, kChachaBlock, 0, st>>>(data, offs, segs, blk_base, n,
                                                             refs, out, prio ? 1u : 0u);
   return hipGetLastError();
@@ -2402,7 +2414,8 @@ hipError_t launch_slice_gather(const uint8_t* ctext, const uint64_t* chunk_offs,
                                uint8_t* out, int num_cus, hipStream_t st) {
   if (nblocks == 0) return hipSuccess;
   const uint64_t need = (nblocks + kChachaBlock - 1) / kChachaBlock, full = (uint64_t)num_cus * 32;
-  chacha_slice_gather_kernel<<<(unsigned)(need < full ? need : full), kChachaBlock, 0, st>>>(
+  chacha_slice_gather_kernel<<<capped_grid(need < full ? need : full, Knob::ChachaGrid),
+                               kChachaBlock, 0, st>>>(
       ctext, chunk_offs, refs, ok, slices, out_off, blk_base, n, out);
   return hipGetLastError();
 }

@@ -131,6 +131,7 @@ struct pfscdc_ctx {
   uint32_t options = 0;
   float get_ms = 0.f;
   float create_ms = 0.f, create_hash_ms = 0.f;
+  int create_form = -1;  // the last chunk.Create batch's Ref.Id pass: 0 fused, 1 split, -1 none
   hipEvent_t cev = nullptr;  // create_refs: between the content-hash and the Ref.Id passes
   hipEvent_t wev = nullptr;  // pfscdc_stream_wait: the caller's stream position
   hipStream_t aux_stream = nullptr;      // create_refs: the second Ref.Id stream (lazy)
@@ -1389,6 +1390,12 @@ int pfscdc_last_create_timings(pfscdc_ctx* c, float out[2]) {
   return PFSCDC_OK;
 }
 
+int pfscdc_last_create_form(pfscdc_ctx* c, int* split) {
+  if (!c || !split) return PFSCDC_EINVAL;
+  *split = c->create_form;
+  return PFSCDC_OK;
+}
+
 int pfscdc_last_get_ms(pfscdc_ctx* c, float* ms) {
   if (!c || !ms) return PFSCDC_EINVAL;
   *ms = c->get_ms;
@@ -1933,6 +1940,7 @@ int create_refs_device(pfscdc_ctx* c, const uint8_t* data, uint64_t nbytes, cons
                              hipMemcpyDeviceToHost, st));
   c->cr.active = true;
   c->cr.split = split;
+  c->create_form = split ? 1 : 0;
   c->cr.k = k;
   c->cr.nr = nr;
   c->cr.hashes = hashes;

@@ -40,7 +40,7 @@ static_assert(sizeof(pfscdc_slice) == 24, "slice record layout");
 
 // Tuning knobs (knobs.cpp): process-wide integers, read from the environment once.
 enum class Knob : int {
-  ScanSkip, ScanCutSkip, ScanGrid,
+  ScanSkip, ScanCutSkip, ScanGrid, HashGrid, ChachaGrid,
   HashBinBytes, HashWaves, HashFair, HashFairEvery,
   RefIdSplit, CommitTwoSets, CommitLongPct,
   UwWorkers, UwInflight, UwMirror, UwIndexGrouped, UwArenaPoolBytes, CtxCache, CopyThreads,

@@ -464,8 +464,9 @@ def test_reference_params_random_batches_equal_oracle(case):
 @pytest.mark.parametrize("case", fuzz_cases(8))
 def test_knobs_never_change_results(knob, case):
     """no knob changes a result.  Random layouts and parameters under random
-    settings of every scan and hash knob at once (workgroup cap, both skips, hash bins, waves
-    per SIMD, fair share and its period), device-resident or host input."""
+    settings of every scan and hash knob at once (workgroup caps of the scan, the hash and the
+    ChaCha20 launches, both skips, hash bins, waves per SIMD, fair share and its period),
+    device-resident or host input."""
     import torch
 
     rng = np.random.default_rng(12000 + case)
@@ -480,6 +481,9 @@ def test_knobs_never_change_results(knob, case):
     knob("PFSCDC_HASH_WAVES", int(rng.integers(0, 3)))
     knob("PFSCDC_HASH_FAIR", int(rng.integers(0, 2)))
     knob("PFSCDC_HASH_FAIR_EVERY", int(rng.choice([8, 16, 256, 4096])))
+    caps = np.random.default_rng(13000 + case)  # their own stream: the layouts stay as they were
+    knob("PFSCDC_HASH_GRID", int(caps.choice([0, 1, 3, 64])))
+    knob("PFSCDC_CHACHA_GRID", int(caps.choice([0, 1, 3, 64])))
     lens, total = [], 0
     for _ in range(int(rng.integers(1, 120))):
         n = int(rng.integers(0, min(3 * p.max, 8 << 20))) if rng.random() < 0.7 else \

@@ -18,39 +18,12 @@ from oracle import chunker as Ch
 from pfs_amd import _lib
 from pfs_amd import chunk as pc
 from pfs_amd.cdc import ChunkParams, Chunker, synthetic_bytes
+from stored_chunks import Stored
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = Ch.Params(average_bits=12, seed=1, min=2000, max=30000)  # as tests/test_gpu_refid.py
-
-
-class Stored:
-    """A batch of chunks as chunk.Create(CreateOptions{}) stores them, back to back."""
-
-    def __init__(self, sizes, seed):
-        self.offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
-        self.plain = synthetic_bytes(self.offs, seed)
-        self.chunks = [self.plain[int(a):int(b)].tobytes()
-                       for a, b in zip(self.offs[:-1], self.offs[1:])]
-        self.refs = np.zeros(len(sizes), dtype=_lib.ref_dtype())
-        self.orefs, self.store, ctexts = [], {}, []
-        for i, ch in enumerate(self.chunks):
-            rid, dek = Ch.create_ref_id(ch)
-            ct = Ch.chacha20_xor(dek, ch)
-            self.refs[i]["id"] = np.frombuffer(rid, dtype=np.uint8)
-            self.refs[i]["dek"] = np.frombuffer(dek, dtype=np.uint8)
-            self.orefs.append(Ch.Ref(size_bytes=len(ch), edge=False, id=rid, dek=dek))
-            self.store[rid] = ct
-            ctexts.append(ct)
-        self.ctext = np.frombuffer(b"".join(ctexts), dtype=np.uint8).copy()
-
-    def oracle(self, slices) -> bytes:
-        return b"".join(Ch.read_data_ref(self.store, Ch.DataRef(self.orefs[c], b"", o, z))
-                        for c, o, z in slices)
-
-    def sliced(self, slices) -> bytes:
-        return b"".join(self.chunks[c][o:o + z] for c, o, z in slices)
 
 
 @pytest.fixture(scope="module")
