@@ -193,6 +193,57 @@ int pfscdc_read_slices(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes, int 
  * hash pass and the id compare), out[1] the sliced decrypt-and-gather kernel. */
 int pfscdc_last_read_timings(pfscdc_ctx* ctx, float out[2]);
 
+/* ---- GetFileTAR (api_server.go:508-531,578-593; fileset/util.go:42-53; tarutil/tar.go:35-40) --
+ * The stream getFileTar writes for files f_0 .. f_{n-1}: per file a 512-byte USTAR header as
+ * Go's archive/tar forms it for Header{Name, Size} (every other field zero), the file's bytes,
+ * zeros to the next multiple of 512; after the last file 1,024 zero bytes.  total =
+ * sum(512 + roundup512(size_i)) + 1024.  The header layout is restated from archive/tar's
+ * source; like everything else here it has not been held against a Go run (README "Scope and
+ * correctness"), and Python's tarfile reads the stream back.
+ * Not implemented: the entries Go writes PAX records for, i.e. a name that is not pure ASCII
+ * 0x01-0x7F, a name longer than 100 bytes that splitUSTARPath cannot split (prefix <= 155 and
+ * suffix 1-100 bytes around a '/'), a size above 077777777777 (8 GiB - 1).  Every entry point
+ * below returns PFSCDC_EUNSUPPORTED for them and those with a ctx name the file in
+ * pfscdc_last_error.  PFSCDC_EINVAL: an empty name, or a directory (name ending in '/') that
+ * has pieces or a size. */
+typedef struct pfscdc_tar_file {
+  const char* path;  /* index.Index.Path, NUL-terminated */
+  uint32_t first;    /* its pieces are [first, first + count) of the slice / DataRef array */
+  uint32_t count;
+} pfscdc_tar_file;
+
+/* The header block of one entry.  Host only: the specification tar_frame_kernel is tested
+ * against. */
+int pfscdc_tar_header(const char* path, uint64_t size, uint8_t out[512]);
+/* Where the entries lie: sizes[i] = file i's size (the sum of its pieces' sizes);
+ * entry_offsets (nfiles + 1 entries, nullable): entry i = stream bytes [entry_offsets[i],
+ * entry_offsets[i + 1]), the trailer begins at entry_offsets[nfiles]; *total the stream's
+ * length.  Host only: what a caller sizes its buffers and windows with. */
+int pfscdc_tar_layout(const pfscdc_tar_file* files, uint32_t nfiles, const uint64_t* sizes,
+                      uint64_t* entry_offsets, uint64_t* total);
+/* Stream bytes [begin, min(begin + len, total)) of the files' tar stream into out (*nwritten of
+ * them, nullable), over a batch of stored chunks as pfscdc_read_slices takes it: file i's
+ * content is the concatenation of slices [first, first + count).  begin must be a multiple of
+ * 512, and so must len unless the window reaches the end of the stream, so a header is never
+ * cut; content is cut anywhere.  The slices are clipped to the window on the host: only the
+ * chunks the clipped slices name are uploaded (host ctext) and verified (unless verified[c]),
+ * and only the window's content bytes are decrypted, straight to their place in the stream
+ * (pfscdc_read_slices' gather kernel).  Headers, padding and trailer are formed on the device
+ * by tar_frame_kernel from each file's name and size; every byte of the window is written
+ * exactly once and out is never cleared first.  chunk_ok as for pfscdc_read_slices; the content
+ * bytes of a chunk that is not ok are zeros, the headers are written all the same.
+ * out: device pointer if out_on_device, else host memory, at any alignment.  Window and name
+ * errors are returned before any GPU call.  Synchronous on the ctx stream, as
+ * pfscdc_read_slices. */
+int pfscdc_read_tar(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes, int ctext_on_device,
+                    const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
+                    const uint8_t* verified, const pfscdc_tar_file* files, uint32_t nfiles,
+                    const pfscdc_slice* slices, uint32_t nslices, uint64_t begin, uint64_t len,
+                    void* out, int out_on_device, uint8_t* chunk_ok, uint64_t* nwritten);
+/* Device time (ms) tar_frame_kernel took in the last pfscdc_read_tar / pfscdc_store_read_tar
+ * (0 after a read without framing); verification and gather are pfscdc_last_read_timings'. */
+int pfscdc_last_frame_ms(pfscdc_ctx* ctx, float* ms);
+
 /* chunk.Create(ctx, CreateOptions{}, chunk, createFunc) (transform.go:26-46) for a batch of
  * formed chunks, the upload half of processChunk (writer.go:233-271): chunk i is bytes
  * [chunk_offsets[i], chunk_offsets[i+1]) (offsets as for pfscdc_get_chunks).  refs[i] gets
@@ -390,6 +441,15 @@ uint64_t pfscdc_store_count(const pfscdc_store* s);
 int pfscdc_store_read(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_full_dataref* drs,
                       uint32_t n, void* out, uint64_t out_cap, int out_on_device,
                       uint64_t* nwritten);
+/* getFileTar against a store: pfscdc_read_tar's window over files whose pieces are the DataRefs
+ * drs[first, first + count).  The batch is the distinct chunks of the DataRefs that meet the
+ * window, uploaded and verified once each.  out_cap: bytes out can take, at least the window's.
+ * Errors as pfscdc_store_read's (PFSCDC_ENOTFOUND / PFSCDC_ECORRUPT: nothing is written to out)
+ * and pfscdc_read_tar's. */
+int pfscdc_store_read_tar(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_tar_file* files,
+                          uint32_t nfiles, const pfscdc_full_dataref* drs, uint32_t ndrs,
+                          uint64_t begin, uint64_t len, void* out, uint64_t out_cap,
+                          int out_on_device, uint64_t* nwritten);
 
 /* batch_bytes: flush threshold for buffered file bytes (0 = 1 GiB).  If ctx has
  * PFSCDC_OPT_REF_IDS set when the writer is created, every chunk also gets its Ref

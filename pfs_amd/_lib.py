@@ -63,6 +63,8 @@ EXPORTED = [
     "pfscdc_group_index_device", "pfscdc_group_last_timings", "pfscdc_uw_create_group",
     "pfscdc_group_scan_stream",
     "pfscdc_read_slices", "pfscdc_last_read_timings", "pfscdc_store_read",
+    "pfscdc_tar_header", "pfscdc_tar_layout", "pfscdc_read_tar", "pfscdc_last_frame_ms",
+    "pfscdc_store_read_tar",
 ]
 
 
@@ -93,6 +95,22 @@ class ChunkRef(C.Structure):
 class FullDataRef(C.Structure):
     _fields_ = [("ref", RefC), ("ref_size", C.c_int64), ("edge", C.c_int32),
                 ("reserved", C.c_int32), ("data", DataRef)]
+
+
+class TarFile(C.Structure):
+    _fields_ = [("path", C.c_char_p), ("first", C.c_uint32), ("count", C.c_uint32)]
+
+
+def tar_files(files):
+    """pfscdc_tar_file array of (path, first, count) triples; a path that cannot be a C string
+    (an embedded NUL) is a ValueError."""
+    arr = (TarFile * max(1, len(files)))()
+    for i, (path, first, count) in enumerate(files):
+        p = path.encode() if isinstance(path, str) else bytes(path)
+        if b"\0" in p:
+            raise ValueError(f"tar entry {path!r}: NUL in the name")
+        arr[i] = TarFile(p, first, count)
+    return arr
 
 
 class AnnotationOut(C.Structure):
@@ -281,6 +299,13 @@ def load() -> C.CDLL:
                                          vp, vp]),
             "pfscdc_last_read_timings": (i32, [vp, P(C.c_float)]),
             "pfscdc_store_read": (i32, [vp, vp, P(FullDataRef), u32, vp, u64, i32, P(u64)]),
+            "pfscdc_tar_header": (i32, [C.c_char_p, u64, vp]),
+            "pfscdc_tar_layout": (i32, [P(TarFile), u32, P(u64), P(u64), P(u64)]),
+            "pfscdc_read_tar": (i32, [vp, vp, u64, i32, P(u64), u32, vp, vp, P(TarFile), u32, vp,
+                                      u32, u64, u64, vp, i32, vp, P(u64)]),
+            "pfscdc_last_frame_ms": (i32, [vp, P(C.c_float)]),
+            "pfscdc_store_read_tar": (i32, [vp, vp, P(TarFile), u32, P(FullDataRef), u32, u64,
+                                            u64, vp, u64, i32, P(u64)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

@@ -229,16 +229,10 @@ class Chunker:
         self._check(rc, "get_chunks")
         return res, ok[:n].astype(bool)
 
-    def read_slices(self, ctext, chunk_offsets: Sequence[int], refs: np.ndarray, slices,
-                    out=None, verified=None):
-        """chunk.Reader.Get over a batch of stored chunks (pfscdc_read_slices): the
-        concatenation of plaintext[offset:offset + size] of each slice's chunk.  ``slices``:
-        (chunk, offset, size) triples or a SLICE_DTYPE array; ``ctext``: host bytes/array or a
-        torch uint8 CUDA tensor; ``out``: optional contiguous torch uint8 tensor (CUDA or CPU)
-        or numpy uint8 array of at least the slices' total size, at any alignment;
-        ``verified``: per-chunk marks of chunks verified before (not hashed again).  Returns
-        (plaintext, chunk_ok[nchunks], slice_ok[nslices]); the bytes of a slice whose chunk is
-        not ok are zeros."""
+    # arguments read_slices and read_tar share: a batch of stored chunks, slices of it, out
+
+    @staticmethod
+    def _stored_batch(chunk_offsets, refs, slices, verified):
         offs = _offsets_array(chunk_offsets)
         n = len(offs) - 1
         refs = np.ascontiguousarray(refs, dtype=_lib.ref_dtype())
@@ -251,35 +245,53 @@ class Chunker:
             sl = np.zeros(len(slices), dtype=sdt)
             for i, (ch, o, z) in enumerate(slices):
                 sl[i] = (ch, 0, o, z)
-        ns = len(sl)
-        total = int(sl["size"].sum()) if ns else 0
         ver = None
         if verified is not None:
             ver = np.ascontiguousarray(np.asarray(verified).astype(np.uint8))
             if len(ver) != n:
                 raise ValueError("one verified mark per chunk")
-        self._after_torch(ctext, out)
+        return offs, n, refs, sl, len(sl), ver
+
+    def _ctext_arg(self, ctext):
         if hasattr(ctext, "is_cuda") and ctext.is_cuda:
             if ctext.dtype.itemsize != 1 or not ctext.is_contiguous():
                 raise ValueError("device ctext must be a contiguous uint8 tensor")
-            cptr, nbytes, con = ctext.data_ptr(), ctext.numel(), 1
-        else:
-            arr = np.ascontiguousarray(np.frombuffer(ctext, dtype=np.uint8)
-                                       if isinstance(ctext, (bytes, bytearray)) else ctext,
-                                       dtype=np.uint8)
-            cptr, nbytes, con = (arr.ctypes.data if arr.size else None), arr.size, 0
-            self._get_keep = arr
+            return ctext.data_ptr(), ctext.numel(), 1
+        arr = np.ascontiguousarray(np.frombuffer(ctext, dtype=np.uint8)
+                                   if isinstance(ctext, (bytes, bytearray)) else ctext,
+                                   dtype=np.uint8)
+        self._get_keep = arr
+        return (arr.ctypes.data if arr.size else None), arr.size, 0
+
+    @staticmethod
+    def _out_arg(out, need: int, what: str):
+        """(result object, pointer, on_device) of an optional out of at least need bytes."""
         if out is None:
-            res = np.empty(total, dtype=np.uint8)
-            optr, oon = (res.ctypes.data if total else None), 0
-        elif isinstance(out, np.ndarray):
-            if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < total:
-                raise ValueError("out must be a contiguous uint8 array of the slices' size")
-            res, optr, oon = out, (out.ctypes.data if out.size else None), 0
-        else:
-            if out.dtype.itemsize != 1 or not out.is_contiguous() or out.numel() < total:
-                raise ValueError("out must be a contiguous uint8 tensor of the slices' size")
-            res, optr, oon = out, (out.data_ptr() if out.numel() else None), int(out.is_cuda)
+            res = np.empty(need, dtype=np.uint8)
+            return res, (res.ctypes.data if need else None), 0
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < need:
+                raise ValueError(f"out must be a contiguous uint8 array of {what}")
+            return out, (out.ctypes.data if out.size else None), 0
+        if out.dtype.itemsize != 1 or not out.is_contiguous() or out.numel() < need:
+            raise ValueError(f"out must be a contiguous uint8 tensor of {what}")
+        return out, (out.data_ptr() if out.numel() else None), int(out.is_cuda)
+
+    def read_slices(self, ctext, chunk_offsets: Sequence[int], refs: np.ndarray, slices,
+                    out=None, verified=None):
+        """chunk.Reader.Get over a batch of stored chunks (pfscdc_read_slices): the
+        concatenation of plaintext[offset:offset + size] of each slice's chunk.  ``slices``:
+        (chunk, offset, size) triples or a SLICE_DTYPE array; ``ctext``: host bytes/array or a
+        torch uint8 CUDA tensor; ``out``: optional contiguous torch uint8 tensor (CUDA or CPU)
+        or numpy uint8 array of at least the slices' total size, at any alignment;
+        ``verified``: per-chunk marks of chunks verified before (not hashed again).  Returns
+        (plaintext, chunk_ok[nchunks], slice_ok[nslices]); the bytes of a slice whose chunk is
+        not ok are zeros."""
+        offs, n, refs, sl, ns, ver = self._stored_batch(chunk_offsets, refs, slices, verified)
+        total = int(sl["size"].sum()) if ns else 0
+        self._after_torch(ctext, out)
+        cptr, nbytes, con = self._ctext_arg(ctext)
+        res, optr, oon = self._out_arg(out, total, "the slices' size")
         cok = np.zeros(max(n, 1), dtype=np.uint8)
         sok = np.zeros(max(ns, 1), dtype=np.uint8)
         rc = self.lib.pfscdc_read_slices(self.ctx, cptr, nbytes, con,
@@ -296,6 +308,45 @@ class Chunker:
         out = (C.c_float * 2)()
         self._check(self.lib.pfscdc_last_read_timings(self.ctx, out), "read_timings")
         return {"verify": out[0], "gather": out[1]}
+
+    def read_tar(self, ctext, chunk_offsets: Sequence[int], refs: np.ndarray, files, slices,
+                 begin: int = 0, length: Optional[int] = None, out=None, verified=None):
+        """One window of the tar stream getFileTar writes for ``files`` (pfscdc_read_tar), over
+        a batch of stored chunks as ``read_slices`` takes it.  ``files``: (path, first, count)
+        triples, file i's content being slices [first, first + count); ``begin``/``length``:
+        the window (multiples of 512 unless it reaches the stream's end; None = to the end);
+        ``out``: optional contiguous torch uint8 tensor (CUDA or CPU) or numpy uint8 array of
+        at least the window's size.  Returns (stream bytes, chunk_ok[nchunks], nwritten)."""
+        offs, n, refs, sl, ns, ver = self._stored_batch(chunk_offsets, refs, slices, verified)
+        tf = _lib.tar_files(files)
+        sizes = np.array([int(sl["size"][f:f + k].sum()) for _, f, k in files], dtype=np.uint64)
+        total = C.c_uint64()
+        rc = self.lib.pfscdc_tar_layout(tf, len(files), sizes.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        None, C.byref(total))
+        if rc == 0:  # (else pfscdc_read_tar reports the same error with the file's name)
+            window = max(0, min(total.value - begin, total.value if length is None else length))
+        else:
+            window = 0
+        self._after_torch(ctext, out)
+        cptr, nbytes, con = self._ctext_arg(ctext)
+        res, optr, oon = self._out_arg(out, window, "the window's size")
+        cok = np.zeros(max(n, 1), dtype=np.uint8)
+        nw = C.c_uint64()
+        rc = self.lib.pfscdc_read_tar(self.ctx, cptr, nbytes, con,
+                                      offs.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                      refs.ctypes.data if n else None,
+                                      ver.ctypes.data if ver is not None and n else None,
+                                      tf, len(files), sl.ctypes.data if ns else None, ns,
+                                      begin, total.value if length is None else length,
+                                      optr, oon, cok.ctypes.data, C.byref(nw))
+        self._check(rc, "read_tar")
+        return res, cok[:n].astype(bool), nw.value
+
+    def last_frame_ms(self) -> float:
+        """Device ms of tar_frame_kernel in the last read_tar / store tar read."""
+        ms = C.c_float()
+        self._check(self.lib.pfscdc_last_frame_ms(self.ctx, C.byref(ms)), "frame_ms")
+        return ms.value
 
     def form_chunks(self, stream_file_begin: Optional[Sequence[int]] = None):
         """Chunks chunk.Writer forms over the last scan's files (pfscdc_form_chunks), each

@@ -2073,6 +2073,96 @@ __global__ void verify_ids_kernel(const pfscdc_segment* __restrict__ segs, uint3
 }
 #undef PFS_CQR
 
+// 5f. GetFileTAR framing (api_server.go:578-593, fileset/util.go:42-53): everything of one
+// window [wbegin, wend) of the tar stream that is not file content, i.e. the 512-byte USTAR
+// headers, each entry's zero padding up to the next multiple of 512 and the trailer's two zero
+// blocks.  The content bytes are chacha_slice_gather_kernel's (its out_off is the tar layout):
+// the two kernels write disjoint bytes and every byte of the window exactly once, so the window
+// is never cleared and the launches need no order between them.  One wave per item, grid-stride
+// over the n entries that meet the window plus the two trailer blocks; no wave waits for
+// another.  Byte j of a header (Go's archive/tar for Header{Name, Size}, restated in
+// pfscdc_tar_header) depends only on j, the name and the size, so lane l forms bytes
+// [8 l, 8 l + 8) in a register: name and prefix bytes come from the packed name table, the
+// rest from j.  The checksum (all 512 bytes, its own field read as spaces) is a wave reduction
+// of the lanes' byte sums, put into bytes 148-155 by lanes 18 and 19, which own them.  A header
+// lies at a multiple of 512 in the stream, but the window lies anywhere in memory: each lane
+// stores its 8 bytes with one unaligned store.  Windows begin and end on multiples of 512 (or
+// at the stream's end), so a header or trailer block is inside whole or not at all; padding is
+// clipped to the window, whole 8-byte pieces as one store and the cut piece byte by byte.
+constexpr int kTarBlock = 256;
+
+PFS_DEV uint32_t tar_header_byte(uint32_t j, const uint8_t* __restrict__ name, uint32_t len,
+                                 int32_t split, uint64_t size) {
+  if (j < 100) {  // name, or its suffix after the split
+    const uint32_t k = j + (uint32_t)(split + 1);
+    return k < len ? name[k] : 0u;
+  }
+  if (j < 124) return (j - 100) % 8 == 7 ? 0u : '0';  // mode, uid, gid
+  if (j < 136) return j == 135 ? 0u : '0' + (uint32_t)((size >> (3 * (134 - j))) & 7);
+  if (j < 148) return j == 147 ? 0u : '0';  // mtime
+  if (j < 156) return ' ';                  // chksum, as it is summed
+  if (j == 156) return name[len - 1] == '/' ? '5' : '0';
+  if (j < 257) return 0u;  // linkname
+  if (j < 265) return (uint32_t)(uint8_t)"ustar\0" "00"[j - 257];
+  if (j < 329) return 0u;  // uname, gname
+  if (j < 345) return (j - 329) % 8 == 7 ? 0u : '0';  // devmajor, devminor
+  if (j < 500) return split >= 0 && j - 345 < (uint32_t)split ? name[j - 345] : 0u;  // prefix
+  return 0u;
+}
+
+__global__ __launch_bounds__(kTarBlock) void tar_frame_kernel(
+    const TarEntry* __restrict__ entries, const uint8_t* __restrict__ names, uint32_t n,
+    uint64_t wbegin, uint64_t wend, uint64_t total, uint8_t* __restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint64_t nwaves = (uint64_t)gridDim.x * (kTarBlock / 64);
+  for (uint64_t e = (uint64_t)blockIdx.x * (kTarBlock / 64) + wv; e < (uint64_t)n + 2;
+       e += nwaves) {
+    uint64_t z0, z1;  // the item's zero bytes, as stream offsets
+    if (e >= n) {     // a trailer block
+      z0 = total - 1024 + 512 * (e - n);
+      z1 = z0 + 512;
+    } else {
+      const TarEntry en = entries[e];
+      if (en.off >= wbegin && en.off < wend) {
+        const uint8_t* name = names + en.name_off;
+        uint64_t v = 0;
+        uint32_t sum = 0;
+#pragma unroll 1  // (8 copies of the case analysis spill SGPRs: 83 VGPRs against 22)
+        for (uint32_t k = 0; k < 8; k++) {
+          const uint32_t b = tar_header_byte(8 * lane + k, name, en.name_len, en.split, en.size);
+          v |= (uint64_t)b << (8 * k);
+          sum += b;
+        }
+        for (int o = 32; o > 0; o >>= 1) sum += (uint32_t)__shfl_xor((int)sum, o, 64);
+        // 6 octal digits, NUL, space: bytes 148-151 are lane 18's upper half, 152-155 lane 19's
+        // lower half
+        if (lane == 18)
+          v = (v & 0xffffffffull) | (uint64_t)('0' + ((sum >> 15) & 7)) << 32 |
+              (uint64_t)('0' + ((sum >> 12) & 7)) << 40 | (uint64_t)('0' + ((sum >> 9) & 7)) << 48 |
+              (uint64_t)('0' + ((sum >> 6) & 7)) << 56;
+        if (lane == 19)
+          v = (v & ~0xffffffffull) | (uint64_t)('0' + ((sum >> 3) & 7)) |
+              (uint64_t)('0' + (sum & 7)) << 8 | (uint64_t)' ' << 24;
+        __builtin_memcpy(out + (en.off - wbegin) + 8 * lane, &v, 8);
+      }
+      z0 = en.off + 512 + en.size;
+      z1 = en.off + 512 + ((en.size + 511) & ~511ull);
+    }
+    z0 = z0 > wbegin ? z0 : wbegin;
+    z1 = z1 < wend ? z1 : wend;
+    const uint64_t a = z0 + 8 * lane;  // at most 512 zero bytes per item: 8 per lane
+    if (a < z1) {
+      if (z1 - a >= 8) {
+        const uint64_t zero = 0;
+        __builtin_memcpy(out + (a - wbegin), &zero, 8);
+      } else {
+        for (uint64_t t = a; t < z1; t++) out[t - wbegin] = 0;
+      }
+    }
+  }
+}
+
 // 5c. BLAKE2b-256, one lane per segment.  No cross-lane traffic at all: the 16-word state,
 // the chaining value and the message block live in the lane's registers, and the sigma
 // schedule is resolved at compile time (every round fully unrolled), so a block costs the
@@ -2417,6 +2507,20 @@ hipError_t launch_slice_gather(const uint8_t* ctext, const uint64_t* chunk_offs,
   chacha_slice_gather_kernel<<<capped_grid(need < full ? need : full, Knob::ChachaGrid),
                                kChachaBlock, 0, st>>>(
       ctext, chunk_offs, refs, ok, slices, out_off, blk_base, n, out);
+  return hipGetLastError();
+}
+
+// Launch width of tar_frame_kernel: workgroups = min(ceil((n + 2) / 4), 8 * num_cus), capped by
+// the PFSCDC_CHACHA_GRID knob; 4 waves each, one item (entry or trailer block) per wave and
+// pass.  8 workgroups of 4 waves fill a CU's 32 wave slots.
+hipError_t launch_tar_frame(const TarEntry* d_entries, const uint8_t* d_names, uint32_t n,
+                            uint64_t begin, uint64_t end, uint64_t total, uint8_t* out,
+                            int num_cus, hipStream_t st) {
+  if (end <= begin) return hipSuccess;
+  const uint64_t per = kTarBlock / 64, need = ((uint64_t)n + 2 + per - 1) / per,
+                 full = (uint64_t)num_cus * 8;
+  tar_frame_kernel<<<capped_grid(need < full ? need : full, Knob::ChachaGrid), kTarBlock, 0,
+                     st>>>(d_entries, d_names, n, begin, end, total, out);
   return hipGetLastError();
 }
 

@@ -31,7 +31,7 @@ constexpr KnobDef kDefs[(int)Knob::kCount] = {
     {"PFSCDC_SCAN_CUTSKIP", 1, 0, 1},       // ... and min - 1 past every settled cut
     {"PFSCDC_SCAN_GRID", 0, 0, 1 << 20},    // scan workgroups cap (0: one per CU)
     {"PFSCDC_HASH_GRID", 0, 0, 1 << 20},    // BLAKE2b workgroups cap, every mode (0: none)
-    {"PFSCDC_CHACHA_GRID", 0, 0, 1 << 20},  // ChaCha20 pass / slice gather workgroups cap
+    {"PFSCDC_CHACHA_GRID", 0, 0, 1 << 20},  // ChaCha20 pass / slice gather / tar framing cap
     {"PFSCDC_HASH_BIN_BYTES", -1, -1, kMax},  // hash bins: -1 auto, 0 none, else bin bytes
     {"PFSCDC_HASH_WAVES", 0, 0, 8},         // hash waves per SIMD (0: by chain length)
     {"PFSCDC_HASH_FAIR", 1, 0, 1},          // fair-share issue priority with hash bins

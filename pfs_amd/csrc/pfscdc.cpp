@@ -126,8 +126,15 @@ struct pfscdc_ctx {
   PinnedBuf<pfscdc_slice> h_rslices;
   PinnedBuf<uint64_t> h_rmeta;
   PinnedBuf<uint8_t> h_rok;
-  hipEvent_t rev[3] = {nullptr, nullptr, nullptr};  // before the verification, the gather, after
+  // read_tar: the window's entries and their packed names (tar_frame_kernel)
+  DevBuf<TarEntry> d_tar;
+  DevBuf<uint8_t> d_tnames;
+  PinnedBuf<TarEntry> h_tar;
+  PinnedBuf<uint8_t> h_tnames;
+  // before the verification, the gather, after it, after the tar framing
+  hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};
   float read_ms[2] = {0.f, 0.f};
+  float frame_ms = 0.f;
   uint32_t options = 0;
   float get_ms = 0.f;
   float create_ms = 0.f, create_hash_ms = 0.f;
@@ -378,6 +385,10 @@ int pfscdc_ctx_destroy(pfscdc_ctx* c) {
   c->h_rslices.release();
   c->h_rmeta.release();
   c->h_rok.release();
+  c->d_tar.release();
+  c->d_tnames.release();
+  c->h_tar.release();
+  c->h_tnames.release();
   for (auto& e : c->rev)
     if (e) (void)hipEventDestroy(e);
   if (c->d_table) (void)hipFree(c->d_table);
@@ -1418,6 +1429,50 @@ int pfscdc_last_read_timings(pfscdc_ctx* c, float out[2]) {
   return PFSCDC_OK;
 }
 
+int pfscdc_last_frame_ms(pfscdc_ctx* c, float* ms) {
+  if (!c || !ms) return PFSCDC_EINVAL;
+  *ms = c->frame_ms;
+  return PFSCDC_OK;
+}
+
+int pfscdc_read_tar(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctext_on_device,
+                    const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
+                    const uint8_t* verified, const pfscdc_tar_file* files, uint32_t nfiles,
+                    const pfscdc_slice* slices, uint32_t nslices, uint64_t begin, uint64_t len,
+                    void* out, int out_on_device, uint8_t* chunk_ok, uint64_t* nwritten) {
+  if (!c) return PFSCDC_EINVAL;
+  if (nwritten) *nwritten = 0;
+  if ((nslices && !slices) || (nchunks && !chunk_offsets))
+    return fail(c, PFSCDC_EINVAL, "NULL argument");
+  std::vector<uint64_t> sizes(nslices);
+  for (uint32_t i = 0; i < nslices; i++) {  // every slice, inside the window or not
+    const pfscdc_slice& s = slices[i];
+    if (s.chunk >= nchunks) return fail(c, PFSCDC_EINVAL, "slice names a chunk >= nchunks");
+    if (chunk_offsets[s.chunk + 1] < chunk_offsets[s.chunk])
+      return fail(c, PFSCDC_EINVAL, "chunk_offsets must be nondecreasing");
+    const uint64_t csize = chunk_offsets[s.chunk + 1] - chunk_offsets[s.chunk];
+    if (s.offset > csize || s.size > csize - s.offset)
+      return fail(c, PFSCDC_EINVAL, "slice reaches past the end of its chunk");
+    sizes[i] = s.size;
+  }
+  TarPlan plan;
+  int rc = tar_plan(files, nfiles, sizes.data(), nslices, begin, len, &plan);
+  if (rc) return fail(c, rc, plan.err);
+  std::vector<pfscdc_slice> clipped(plan.pieces.size());
+  for (size_t k = 0; k < clipped.size(); k++) {
+    const TarPiece& p = plan.pieces[k];
+    clipped[k] = pfscdc_slice{slices[p.src].chunk, 0, slices[p.src].offset + p.skip, p.size};
+  }
+  const uint64_t none[1] = {0};
+  rc = read_slices_impl(c, ctext, nbytes, ctext_on_device,
+                        !chunk_offsets && !nchunks && !nbytes ? none : chunk_offsets, nchunks,
+                        refs, verified, clipped.data(), (uint32_t)clipped.size(), out,
+                        out_on_device, chunk_ok, nullptr, false, &plan);
+  if (rc) return rc;
+  if (nwritten) *nwritten = plan.end - plan.begin;
+  return PFSCDC_OK;
+}
+
 void* pfscdc_host_alloc(uint64_t nbytes) {
   void* p = nullptr;
   if (hipHostMalloc(&p, nbytes ? nbytes : 1, hipHostMallocDefault) != hipSuccess) return nullptr;
@@ -1478,6 +1533,7 @@ int pfscdc_fill_synthetic(pfscdc_ctx* c, void* dev_bytes, const uint64_t* file_o
 namespace pfscdc {
 
 int ctx_device(const pfscdc_ctx* c) { return c->device; }
+int ctx_fail(pfscdc_ctx* c, int code, const std::string& msg) { return fail(c, code, msg); }
 hipError_t ctx_group_buffers(pfscdc_ctx* c, uint64_t bytes, bool ctext, uint8_t** d,
                              uint8_t** dct) {
   hipError_t e = c->d_group.ensure(bytes);
@@ -1566,7 +1622,7 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
                      const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
                      const uint8_t* verified, const pfscdc_slice* slices, uint32_t nslices,
                      void* out, int out_on_device, uint8_t* chunk_ok, uint8_t* slice_ok,
-                     bool strict) {
+                     bool strict, const TarPlan* tar) {
   if (!c) return PFSCDC_EINVAL;
   if (c->pending) return fail(c, PFSCDC_ESTATE, "read_slices during a pending scan");
   if (!chunk_offsets || (nchunks && (!refs || !chunk_ok)) || (nbytes && !ctext) ||
@@ -1593,13 +1649,14 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
     nblocks += (s.offset + s.size - 1) / 64 - s.offset / 64 + 1;
     m++;
   }
-  if (total && !out) return fail(c, PFSCDC_EINVAL, "NULL argument");
-  if (ctext_on_device && out_on_device && total && nbytes) {
+  const uint64_t out_bytes = tar ? tar->end - tar->begin : total;  // tar: the whole window
+  if (out_bytes && !out) return fail(c, PFSCDC_EINVAL, "NULL argument");
+  if (ctext_on_device && out_on_device && out_bytes && nbytes) {
     const uintptr_t a = (uintptr_t)ctext, b = (uintptr_t)out;
-    if (a < b + total && b < a + nbytes)
+    if (a < b + out_bytes && b < a + nbytes)
       return fail(c, PFSCDC_EINVAL, "out overlaps ctext");
   }
-  if (nchunks == 0) return PFSCDC_OK;
+  if (nchunks == 0 && !tar) return PFSCDC_OK;
   c->scan_valid = false;
   c->nsegs = 0;  // the staging below overwrites the last scan's records
   c->have_refs = false;
@@ -1643,7 +1700,7 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
       const pfscdc_slice& s = slices[i];
       if (!s.size) continue;
       c->h_rslices.p[k] = s;
-      h_out_off[k] = o;
+      h_out_off[k] = tar ? tar->pieces[i].out_off : o;
       h_blk[k] = b;
       o += s.size;
       b += (s.offset + s.size - 1) / 64 - s.offset / 64 + 1;
@@ -1666,21 +1723,48 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
     in = (const uint8_t*)ctext;
   } else {
     HIP_OK(c, c->d_data.ensure(nbytes + 64));
-    if (nbytes) HIP_OK(c, hipMemcpyAsync(c->d_data.p, ctext, nbytes, hipMemcpyHostToDevice, st));
+    if (tar) {  // only the chunks the window's slices name, each run of them as one copy
+      std::vector<uint8_t> named(nchunks, 0);
+      for (uint32_t i = 0; i < nslices; i++) named[slices[i].chunk] = 1;
+      for (uint32_t i = 0, j; i < nchunks; i = j) {
+        for (j = i + 1; named[i] && j < nchunks && named[j];) j++;
+        const uint64_t a = chunk_offsets[i], b = chunk_offsets[j];
+        if (named[i] && b > a)
+          HIP_OK(c, hipMemcpyAsync(c->d_data.p + a, (const uint8_t*)ctext + a, b - a,
+                                   hipMemcpyHostToDevice, st));
+      }
+    } else if (nbytes) {
+      HIP_OK(c, hipMemcpyAsync(c->d_data.p, ctext, nbytes, hipMemcpyHostToDevice, st));
+    }
     in = c->d_data.p;
   }
   uint8_t* outp;
   if (out_on_device) {
     outp = (uint8_t*)out;
   } else {
-    HIP_OK(c, c->d_out.ensure(total + 64));
+    HIP_OK(c, c->d_out.ensure(out_bytes + 64));
     outp = c->d_out.p;
+  }
+  const uint32_t nent = tar ? (uint32_t)tar->entries.size() : 0;
+  if (nent) {
+    HIP_OK(c, c->h_tar.ensure(nent));
+    HIP_OK(c, c->d_tar.ensure(nent));
+    HIP_OK(c, c->h_tnames.ensure(tar->names.size()));
+    HIP_OK(c, c->d_tnames.ensure(tar->names.size()));
+    std::memcpy(c->h_tar.p, tar->entries.data(), sizeof(TarEntry) * nent);
+    std::memcpy(c->h_tnames.p, tar->names.data(), tar->names.size());
+    HIP_OK(c, hipMemcpyAsync(c->d_tar.p, c->h_tar.p, sizeof(TarEntry) * nent,
+                             hipMemcpyHostToDevice, st));
+    HIP_OK(c, hipMemcpyAsync(c->d_tnames.p, c->h_tnames.p, tar->names.size(),
+                             hipMemcpyHostToDevice, st));
   }
   HIP_OK(c, hipMemcpyAsync(c->d_offs.p, c->h_offs.p, sizeof(uint64_t) * (nchunks + 1),
                            hipMemcpyHostToDevice, st));
-  HIP_OK(c, hipMemcpyAsync(c->d_refs.p, c->h_refs.p, sizeof(pfscdc_ref) * nchunks,
-                           hipMemcpyHostToDevice, st));
-  HIP_OK(c, hipMemcpyAsync(c->d_rok.p, c->h_rok.p, nchunks, hipMemcpyHostToDevice, st));
+  if (nchunks) {
+    HIP_OK(c, hipMemcpyAsync(c->d_refs.p, c->h_refs.p, sizeof(pfscdc_ref) * nchunks,
+                             hipMemcpyHostToDevice, st));
+    HIP_OK(c, hipMemcpyAsync(c->d_rok.p, c->h_rok.p, nchunks, hipMemcpyHostToDevice, st));
+  }
   if (nh)
     HIP_OK(c, hipMemcpyAsync(c->d_segs.p, c->h_segs.p, sizeof(pfscdc_segment) * nh,
                              hipMemcpyHostToDevice, st));
@@ -1696,7 +1780,8 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
                            c->d_qctr.p, c->num_cus, nbytes, st, false, nullptr,
                            knob_waves(longest, sum, c->num_cus)));
   HIP_OK(c, launch_verify_ids(c->d_segs.p, nh, c->d_refs.p, c->d_rok.p, st));
-  HIP_OK(c, hipMemcpyAsync(c->h_rok.p, c->d_rok.p, nchunks, hipMemcpyDeviceToHost, st));
+  if (nchunks)
+    HIP_OK(c, hipMemcpyAsync(c->h_rok.p, c->d_rok.p, nchunks, hipMemcpyDeviceToHost, st));
   HIP_OK(c, hipEventRecord(c->rev[1], st));
   if (strict) {
     HIP_OK(c, hipStreamSynchronize(st));
@@ -1710,15 +1795,22 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
                                 c->d_rmeta.p, c->d_rmeta.p + m + 1, m, nblocks, outp,
                                 c->num_cus, st));
   HIP_OK(c, hipEventRecord(c->rev[2], st));
-  if (!out_on_device && total)
-    HIP_OK(c, hipMemcpyAsync(out, outp, total, hipMemcpyDeviceToHost, st));
+  if (tar) {
+    HIP_OK(c, launch_tar_frame(c->d_tar.p, c->d_tnames.p, nent, tar->begin, tar->end, tar->total,
+                               outp, c->num_cus, st));
+    HIP_OK(c, hipEventRecord(c->rev[3], st));
+  }
+  if (!out_on_device && out_bytes)
+    HIP_OK(c, hipMemcpyAsync(out, outp, out_bytes, hipMemcpyDeviceToHost, st));
   HIP_OK(c, hipStreamSynchronize(st));
-  std::memcpy(chunk_ok, c->h_rok.p, nchunks);
+  if (nchunks) std::memcpy(chunk_ok, c->h_rok.p, nchunks);
   if (slice_ok)
     for (uint32_t i = 0; i < nslices; i++) slice_ok[i] = c->h_rok.p[slices[i].chunk];
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, c->rev[0], c->rev[1]) == hipSuccess) c->read_ms[0] = ms;
   if (hipEventElapsedTime(&ms, c->rev[1], c->rev[2]) == hipSuccess) c->read_ms[1] = ms;
+  c->frame_ms = 0.f;
+  if (tar && hipEventElapsedTime(&ms, c->rev[2], c->rev[3]) == hipSuccess) c->frame_ms = ms;
   return PFSCDC_OK;
 }
 

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+#include <vector>
+
 #include "../../include/pfscdc.h"
 
 namespace pfscdc {
@@ -212,13 +215,57 @@ hipError_t launch_slice_gather(const uint8_t* ctext, const uint64_t* chunk_offs,
                                const pfscdc_slice* slices, const uint64_t* out_off,
                                const uint64_t* blk_base, uint32_t n, uint64_t nblocks,
                                uint8_t* out, int num_cus, hipStream_t st);
+// One tar entry as tar_frame_kernel takes it: where its header lies in the stream, the size
+// field, and its name in the packed name table (split: index of the '/' that splitUSTARPath
+// cuts at, -1 for none).
+struct TarEntry {
+  uint64_t off;   // stream offset of the 512-byte header
+  uint64_t size;  // content bytes (the padding follows them up to the next multiple of 512)
+  uint32_t name_off;
+  uint16_t name_len;
+  int16_t split;
+};
+static_assert(sizeof(TarEntry) == 24, "tar entry record layout");
+constexpr uint64_t kTarMaxSize = 077777777777ull;  // 11 octal digits: above it Go writes PAX
+// Why a name or size has no USTAR header (nullptr: it has one); *split as TarEntry::split.
+// *rc: PFSCDC_EUNSUPPORTED where Go would write PAX records, PFSCDC_EINVAL for an empty name or
+// a directory (name ending in '/') with content.
+const char* tar_name_check(const char* name, size_t len, uint64_t size, int* split, int* rc);
+// One window [begin, end) of the stream of getFileTar over files whose pieces are
+// [first, first + count) of an array of npieces pieces (slices or DataRefs) of piece_sizes
+// bytes: the entries that meet the window, their names, and the pieces' bytes inside it.
+struct TarPiece {
+  uint32_t src;      // index of the piece in the caller's array
+  uint64_t skip;     // bytes of the piece in front of the window
+  uint64_t size;     // bytes of it inside the window (> 0)
+  uint64_t out_off;  // where they go, relative to begin
+};
+struct TarPlan {
+  uint64_t total = 0, begin = 0, end = 0;
+  std::vector<TarEntry> entries;
+  std::string names;
+  std::vector<TarPiece> pieces;
+  std::string err;
+};
+// PFSCDC_EINVAL / PFSCDC_EUNSUPPORTED with plan->err set; no GPU call
+int tar_plan(const pfscdc_tar_file* files, uint32_t nfiles, const uint64_t* piece_sizes,
+             uint32_t npieces, uint64_t begin, uint64_t len, TarPlan* plan);
+// headers, padding and trailer of plan's window into out (stream byte plan.begin = out[0]);
+// d_entries / d_names: the plan's entries and names on the device
+hipError_t launch_tar_frame(const TarEntry* d_entries, const uint8_t* d_names, uint32_t n,
+                            uint64_t begin, uint64_t end, uint64_t total, uint8_t* out,
+                            int num_cus, hipStream_t st);
+int ctx_fail(pfscdc_ctx* ctx, int code, const std::string& msg);  // sets pfscdc_last_error
 // pfscdc_read_slices; strict: PFSCDC_ECORRUPT, before anything is written to out, if a chunk
-// that a slice names fails verification (pfscdc_store_read)
+// that a slice names fails verification (pfscdc_store_read).  tar (nullable; pfscdc_read_tar):
+// slices are tar->pieces in order, slice i goes to out + tar->pieces[i].out_off instead of
+// behind slice i - 1, only the chunks they name are uploaded from a host ctext, and
+// tar_frame_kernel writes every other byte of the window.
 int read_slices_impl(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes, int ctext_on_device,
                      const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
                      const uint8_t* verified, const pfscdc_slice* slices, uint32_t nslices,
                      void* out, int out_on_device, uint8_t* chunk_ok, uint8_t* slice_ok,
-                     bool strict);
+                     bool strict, const TarPlan* tar = nullptr);
 // segs[i].file += base for i < n (a device group's gathered index: member-local file ids
 // become the commit's)
 hipError_t launch_rebase_files(pfscdc_segment* segs, uint64_t n, uint32_t base, hipStream_t st);

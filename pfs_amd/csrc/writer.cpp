@@ -985,25 +985,23 @@ int pfscdc_store_get(const pfscdc_store* s, const uint8_t id[32], const void** c
 
 uint64_t pfscdc_store_count(const pfscdc_store* s) { return s ? s->objects.size() : 0; }
 
-// Storage.NewReader(dataRefs).Get(w) (storage.go:50-55, reader.go:43-48): the distinct chunks
-// of drs, in order of first use, form one batch of stored chunks; every DataRef is a slice of it.
-int pfscdc_store_read(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_full_dataref* drs,
-                      uint32_t n, void* out, uint64_t out_cap, int out_on_device,
-                      uint64_t* nwritten) {
-  if (!ctx || !s || (n && !drs)) return PFSCDC_EINVAL;
-  if (nwritten) *nwritten = 0;
+// The distinct chunks of a list of DataRefs (by Ref.Id), in order of first use, as one batch of
+// stored chunks for read_slices_impl.
+struct StoreBatch {
   std::map<std::string, uint32_t> index;  // Ref.Id -> chunk of the batch
   std::vector<const std::string*> objs;
   std::vector<pfscdc_ref> refs;
-  std::vector<pfscdc_slice> slices(n);
-  uint64_t total = 0;
-  bool corrupt = false;
-  for (uint32_t i = 0; i < n; i++) {
-    const pfscdc_full_dataref& dr = drs[i];
-    if (dr.ref_size < 0 || dr.data.offset_bytes < 0 || dr.data.size_bytes < 0 ||
-        dr.data.offset_bytes > dr.ref_size ||
-        dr.data.size_bytes > dr.ref_size - dr.data.offset_bytes)
-      return PFSCDC_EINVAL;
+  bool corrupt = false;  // a stored object of another length than its Ref.SizeBytes
+  std::vector<uint64_t> offs;
+  std::vector<uint8_t> ct;
+
+  static bool valid(const pfscdc_full_dataref& dr) {
+    return dr.ref_size >= 0 && dr.data.offset_bytes >= 0 && dr.data.size_bytes >= 0 &&
+           dr.data.offset_bytes <= dr.ref_size &&
+           dr.data.size_bytes <= dr.ref_size - dr.data.offset_bytes;
+  }
+  // dr's chunk in the batch; PFSCDC_ENOTFOUND if the store lacks it
+  int add(const pfscdc_store* s, const pfscdc_full_dataref& dr, uint32_t* chunk) {
     const std::string id((const char*)dr.ref.id, 32);
     auto it = index.find(id);
     if (it == index.end()) {
@@ -1015,23 +1013,90 @@ int pfscdc_store_read(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_full_
     }
     // a stored object of another length than Ref.SizeBytes is not the chunk the DataRef names
     if (objs[it->second]->size() != (uint64_t)dr.ref_size) corrupt = true;
-    slices[i] = pfscdc_slice{it->second, 0, (uint64_t)dr.data.offset_bytes,
+    *chunk = it->second;
+    return PFSCDC_OK;
+  }
+  void concat() {
+    offs.assign(objs.size() + 1, 0);
+    for (size_t k = 0; k < objs.size(); k++) offs[k + 1] = offs[k] + objs[k]->size();
+    ct.resize(offs.back());
+    for (size_t k = 0; k < objs.size(); k++)
+      if (!objs[k]->empty()) std::memcpy(ct.data() + offs[k], objs[k]->data(), objs[k]->size());
+  }
+};
+
+// Storage.NewReader(dataRefs).Get(w) (storage.go:50-55, reader.go:43-48): the distinct chunks
+// of drs, in order of first use, form one batch of stored chunks; every DataRef is a slice of it.
+int pfscdc_store_read(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_full_dataref* drs,
+                      uint32_t n, void* out, uint64_t out_cap, int out_on_device,
+                      uint64_t* nwritten) {
+  if (!ctx || !s || (n && !drs)) return PFSCDC_EINVAL;
+  if (nwritten) *nwritten = 0;
+  StoreBatch b;
+  std::vector<pfscdc_slice> slices(n);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const pfscdc_full_dataref& dr = drs[i];
+    if (!StoreBatch::valid(dr)) return PFSCDC_EINVAL;
+    uint32_t chunk;
+    if (int rc = b.add(s, dr, &chunk)) return rc;
+    slices[i] = pfscdc_slice{chunk, 0, (uint64_t)dr.data.offset_bytes,
                              (uint64_t)dr.data.size_bytes};
     total += (uint64_t)dr.data.size_bytes;
   }
   if (total > out_cap || (total && !out)) return PFSCDC_EINVAL;
-  if (corrupt) return PFSCDC_ECORRUPT;
-  std::vector<uint64_t> offs(objs.size() + 1, 0);
-  for (size_t k = 0; k < objs.size(); k++) offs[k + 1] = offs[k] + objs[k]->size();
-  std::vector<uint8_t> ct(offs.back());
-  for (size_t k = 0; k < objs.size(); k++)
-    if (!objs[k]->empty()) std::memcpy(ct.data() + offs[k], objs[k]->data(), objs[k]->size());
-  std::vector<uint8_t> ok(objs.size() + 1);
-  int rc = pfscdc::read_slices_impl(ctx, ct.data(), ct.size(), 0, offs.data(),
-                                    (uint32_t)objs.size(), refs.data(), nullptr, slices.data(), n,
-                                    out, out_on_device, ok.data(), nullptr, true);
+  if (b.corrupt) return PFSCDC_ECORRUPT;
+  b.concat();
+  std::vector<uint8_t> ok(b.objs.size() + 1);
+  int rc = pfscdc::read_slices_impl(ctx, b.ct.data(), b.ct.size(), 0, b.offs.data(),
+                                    (uint32_t)b.objs.size(), b.refs.data(), nullptr,
+                                    slices.data(), n, out, out_on_device, ok.data(), nullptr,
+                                    true);
   if (rc) return rc;
   if (nwritten) *nwritten = total;
+  return PFSCDC_OK;
+}
+
+// getFileTar (api_server.go:578-593) over a store: the window is planned first, so the batch
+// holds only the chunks of the DataRefs that meet it, in order of first use.
+int pfscdc_store_read_tar(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_tar_file* files,
+                          uint32_t nfiles, const pfscdc_full_dataref* drs, uint32_t ndrs,
+                          uint64_t begin, uint64_t len, void* out, uint64_t out_cap,
+                          int out_on_device, uint64_t* nwritten) {
+  if (!ctx || !s || (ndrs && !drs)) return PFSCDC_EINVAL;
+  if (nwritten) *nwritten = 0;
+  std::vector<uint64_t> sizes(ndrs);
+  for (uint32_t i = 0; i < ndrs; i++) {
+    if (!StoreBatch::valid(drs[i]))
+      return pfscdc::ctx_fail(ctx, PFSCDC_EINVAL, "a DataRef reaches past its chunk");
+    sizes[i] = (uint64_t)drs[i].data.size_bytes;
+  }
+  pfscdc::TarPlan plan;
+  int rc = pfscdc::tar_plan(files, nfiles, sizes.data(), ndrs, begin, len, &plan);
+  if (rc) return pfscdc::ctx_fail(ctx, rc, plan.err);
+  const uint64_t window = plan.end - plan.begin;
+  if (window > out_cap || (window && !out))
+    return pfscdc::ctx_fail(ctx, PFSCDC_EINVAL, "out_cap below the window's bytes");
+  StoreBatch b;
+  std::vector<pfscdc_slice> slices(plan.pieces.size());
+  for (size_t k = 0; k < slices.size(); k++) {
+    const pfscdc::TarPiece& p = plan.pieces[k];
+    const pfscdc_full_dataref& dr = drs[p.src];
+    uint32_t chunk;
+    if (b.add(s, dr, &chunk))
+      return pfscdc::ctx_fail(ctx, PFSCDC_ENOTFOUND, "a chunk id is not in the store");
+    slices[k] = pfscdc_slice{chunk, 0, (uint64_t)dr.data.offset_bytes + p.skip, p.size};
+  }
+  if (b.corrupt)
+    return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT, "a stored chunk's length differs from its Ref's");
+  b.concat();
+  std::vector<uint8_t> ok(b.objs.size() + 1);
+  rc = pfscdc::read_slices_impl(ctx, b.ct.data(), b.ct.size(), 0, b.offs.data(),
+                                (uint32_t)b.objs.size(), b.refs.data(), nullptr, slices.data(),
+                                (uint32_t)slices.size(), out, out_on_device, ok.data(), nullptr,
+                                true, &plan);
+  if (rc) return rc;
+  if (nwritten) *nwritten = window;
   return PFSCDC_OK;
 }
 

@@ -49,6 +49,160 @@ def clean(p: str, is_dir: bool) -> str:
     return out.value.decode()
 
 
+def _tar_error(rc: int, what: str):
+    if rc == _lib.PFSCDC_EUNSUPPORTED:
+        return _lib.PfsCdcError(rc, f"{what}: the entry needs a PAX header (non-ASCII name, a "
+                                    "name over 100 bytes that does not split, or a size above "
+                                    "8 GiB - 1), which is not implemented")
+    return ValueError(f"{what}: empty name, or a directory entry with content")
+
+
+def tar_header(path: str, size: int) -> bytes:
+    """The 512-byte USTAR header Go's archive/tar writes for ``tarutil.NewHeader(path, size)``
+    (tarutil/tar.go:35-40; pfscdc_tar_header).  PfsCdcError(PFSCDC_EUNSUPPORTED) for an entry
+    that needs PAX records, ValueError for an empty name or a directory with a size."""
+    p = path.encode() if isinstance(path, str) else bytes(path)
+    if b"\0" in p or not 0 <= size < 1 << 64:
+        raise ValueError(f"tar entry {path!r}: NUL in the name or a size outside uint64")
+    out = (C.c_uint8 * 512)()
+    rc = _lib.load().pfscdc_tar_header(p, size, out)
+    if rc:
+        raise _tar_error(rc, f"tar entry {path!r}")
+    return bytes(out)
+
+
+def _tar_pieces(files):
+    """(path, first, count) triples and the flat DataRef list of [(path, [DataRef])]."""
+    triples, flat = [], []
+    for path, drs in files:
+        triples.append((path, len(flat), len(drs)))
+        flat.extend(drs)
+    return triples, flat
+
+
+def tar_layout(files):
+    """``(entry_offsets, total)`` of the stream getFileTar writes for ``files``, a list of
+    (path, [DataRef]) (pfscdc_tar_layout): entry i is stream bytes [entry_offsets[i],
+    entry_offsets[i + 1]), the 1,024-byte trailer begins at entry_offsets[len(files)]."""
+    triples, flat = _tar_pieces(files)
+    tf = _lib.tar_files(triples)
+    sizes = (C.c_uint64 * max(1, len(files)))(
+        *[sum(d.size_bytes for d in drs) for _, drs in files])
+    offs = (C.c_uint64 * (len(files) + 1))()
+    total = C.c_uint64()
+    rc = _lib.load().pfscdc_tar_layout(tf, len(files), sizes, offs, C.byref(total))
+    if rc:
+        for path, drs in files:  # name the first file that cannot be written
+            tar_header(path, sum(d.size_bytes for d in drs))
+        raise ValueError("tar_layout: a directory entry with DataRefs")
+    return list(offs), total.value
+
+
+class TarStream:
+    """The stream ``GetFileTAR`` sends for ``files`` (api_server.go:508-531, getFileTar
+    :578-593, fileset.WriteTarEntry util.go:42-53), read from ``storage``'s chunk store in
+    windows (pfscdc_store_read_tar): each window's distinct chunks are uploaded and verified
+    once, only the window's content bytes are decrypted, and headers, padding and trailer are
+    formed on the GPU.  ``storage``: a ``chunk.Storage`` with a store; ``files``: a list of
+    (path, [DataRef]) in stream order.  Errors as ``chunk.Reader``'s: ValueError, KeyError (a
+    chunk missing from the store), PfsCdcError (PFSCDC_ECORRUPT: a chunk failed verification,
+    nothing written; PFSCDC_EUNSUPPORTED: an entry that needs a PAX header)."""
+
+    def __init__(self, storage, files):
+        self.files = [(p, list(drs)) for p, drs in files]
+        self.device = storage.device
+        self._store = storage.store
+        self.entry_offsets, self._total = tar_layout(self.files)
+        self._c = None
+
+    def size(self) -> int:
+        return self._total
+
+    def _window(self, begin: int, length: Optional[int]) -> int:
+        if begin < 0 or begin > self._total or begin % 512:
+            raise ValueError("begin must be a multiple of 512 inside the stream")
+        n = self._total - begin if length is None else min(length, self._total - begin)
+        if n < 0 or (begin + n < self._total and n % 512):
+            raise ValueError("length must be a multiple of 512 unless the window reaches the "
+                             "end of the stream")
+        return n
+
+    def _arrays(self):
+        """The files and DataRefs as the C ABI takes them (built once, checked first)."""
+        from .chunk import _full
+
+        if self._store is None:
+            raise ValueError("the storage has no chunk store to read from")
+        if self._c is None:
+            triples, flat = _tar_pieces(self.files)
+            for i, dr in enumerate(flat):
+                if dr.offset_bytes < 0 or dr.size_bytes < 0 or \
+                        dr.offset_bytes + dr.size_bytes > dr.ref.size_bytes:
+                    raise ValueError(f"DataRef {i} reaches past its chunk")
+            arr = (_lib.FullDataRef * max(1, len(flat)))()
+            for i, d in enumerate(flat):
+                arr[i] = _full(d)
+            self._c = (_lib.tar_files(triples), len(triples), arr, flat)
+        return self._c
+
+    def _read(self, ptr, cap: int, on_device: int, begin: int, n: int, chunker=None) -> int:
+        tf, nfiles, arr, flat = self._arrays()
+        c = chunker if chunker is not None else Chunker(ChunkParams(), self.device)
+        try:
+            nw = C.c_uint64()
+            rc = c.lib.pfscdc_store_read_tar(c.ctx, self._store._s, tf, nfiles, arr,
+                                             len(flat), begin, n, ptr, cap, on_device,
+                                             C.byref(nw))
+            msg = c.lib.pfscdc_last_error(c.ctx)
+        finally:
+            if chunker is None:
+                c.close()
+        if rc == _lib.PFSCDC_ENOTFOUND:
+            for d in flat:
+                self._store.get(d.ref.id)  # raises KeyError for the missing id
+            raise KeyError("chunk not in the store")
+        if rc:
+            raise _lib.PfsCdcError(rc, f"TarStream: {msg.decode() if msg else ''}")
+        return nw.value
+
+    def read(self, begin: int = 0, length: Optional[int] = None) -> bytes:
+        """Stream bytes [begin, begin + length) (None: to the end)."""
+        n = self._window(begin, length)
+        buf = (C.c_uint8 * max(1, n))()
+        got = self._read(buf, n, 0, begin, n)
+        return bytes(memoryview(buf)[:got])
+
+    def read_into(self, tensor, begin: int = 0, length: Optional[int] = None) -> int:
+        """The same window into a contiguous torch uint8 tensor (CUDA: the stream stays on the
+        device); returns the number of bytes written.  Nothing is written on an error."""
+        n = self._window(begin, length)
+        if tensor.dtype.itemsize != 1 or not tensor.is_contiguous():
+            raise ValueError("read_into needs a contiguous uint8 tensor")
+        if tensor.numel() < n:
+            raise ValueError("tensor smaller than the window")
+        if tensor.is_cuda:
+            import torch
+
+            torch.cuda.current_stream(tensor.device).synchronize()  # earlier writes have landed
+        return self._read(tensor.data_ptr() if tensor.numel() else None, tensor.numel(),
+                          int(tensor.is_cuda), begin, n)
+
+    def windows(self, nbytes: int):
+        """Consecutive windows of ``nbytes`` (a multiple of 512) covering the stream, as
+        grpcutil.WithStreamingBytesWriter sends it."""
+        if nbytes <= 0 or nbytes % 512:
+            raise ValueError("window size must be a positive multiple of 512")
+        self._arrays()
+        c = Chunker(ChunkParams(), self.device)  # one context for the whole stream
+        try:
+            buf = (C.c_uint8 * nbytes)()
+            for begin in range(0, self._total, nbytes):
+                got = self._read(buf, nbytes, 0, begin, self._window(begin, nbytes), c)
+                yield bytes(memoryview(buf)[:got])
+        finally:
+            c.close()
+
+
 class Storage:
     """``fileset.Storage`` restricted to the write path, bound to one GPU, or with
     ``devices`` to a device group (one process, several GPUs: pfscdc_uw_create_group deals

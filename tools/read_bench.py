@@ -12,8 +12,16 @@ the gather's (bytes read + bytes written) / ms against benchkit.common.HBM_PEAK_
 gather kernel's share of HBM peak.  Every output is compared with the plaintext before
 anything is printed.  Writes one JSON (default profiles/r7/read_path/read_bench.json).
 
-usage: python tools/read_bench.py [--chunks N] [--chunk-bytes B] [--reps R] [--warmup W]
-                                  [--out PATH]"""
+--tar: the same three layouts as GetFileTAR streams (pfscdc_read_tar, one file per slice),
+alternated in the same process with pfscdc_read_slices over the same slices (the yardstick: its
+code does not change with the tar path).  Per layout: stream bytes, median device ms of the
+verification, the gather and tar_frame_kernel, and read_slices' two figures with their spread.
+The first tar stream of each layout is checked: every file's content against the plaintext,
+sampled headers against pfscdc_tar_header, padding and trailer zero.  Writes
+profiles/r8/read_tar/read_tar.json.
+
+usage: python tools/read_bench.py [--tar] [--chunks N] [--chunk-bytes B] [--reps R]
+                                  [--warmup W] [--out PATH]"""
 import argparse
 import json
 import os
@@ -66,15 +74,89 @@ def check(out, data, cb, runs):
     assert at == out.numel()
 
 
+def check_tar(out, data, cb, sl, names, offs, total):
+    """The tar stream in out: every file's content is the plaintext of its slice, sampled
+    headers are pfscdc_tar_header's, the sampled files' padding and the trailer are zero."""
+    from pfs_amd.fileset import tar_header
+    chunk, off, size = (sl[k].astype(np.int64) for k in ("chunk", "offset", "size"))
+    for i in range(len(sl)):
+        a, b = int(chunk[i]) * cb + int(off[i]), int(offs[i]) + 512
+        if not torch.equal(out[b:b + int(size[i])], data[a:a + int(size[i])]):
+            raise SystemExit(f"read_bench: tar content differs from the plaintext in file {i}")
+    for i in sorted({0, 1, len(sl) // 2, len(sl) - 1} | set(range(0, len(sl), max(1, len(sl) // 61)))):
+        at, z = int(offs[i]), int(size[i])
+        if out[at:at + 512].cpu().numpy().tobytes() != tar_header(names[i], z):
+            raise SystemExit(f"read_bench: tar header {i} differs from pfscdc_tar_header")
+        if int(out[at + 512 + z:int(offs[i + 1])].max().item() if -z % 512 else 0) != 0:
+            raise SystemExit(f"read_bench: tar padding of file {i} is not zero")
+    if int(out[total - 1024:total].max().item()) != 0:
+        raise SystemExit("read_bench: tar trailer is not zero")
+
+
+def tar_rows(args, c, data, ctext, cofs, refs, n, cb):
+    rows = []
+    med = statistics.median
+    for name, (sl, ver, runs) in layouts(n, cb, np.random.default_rng(7)).items():
+        payload = int(sl["size"].sum())
+        names = ["/bench/%s/%07d" % (name, i) for i in range(len(sl))]
+        files = [(p, i, 1) for i, p in enumerate(names)]
+        padded = (sl["size"].astype(np.int64) + 511) // 512 * 512 + 512
+        offs = np.concatenate([[0], np.cumsum(padded)])
+        total = int(offs[-1]) + 1024
+        out = torch.empty(payload, dtype=torch.uint8, device="cuda:0")
+        tout = torch.empty(total, dtype=torch.uint8, device="cuda:0")
+        t_v, t_g, t_f, s_v, s_g = [], [], [], [], []
+        for i in range(args.warmup + args.reps):
+            out.fill_(0xA5)
+            _, cok, _ = c.read_slices(ctext, cofs, refs, sl, out=out, verified=ver)
+            s = c.last_read_timings()
+            if not cok.all():
+                raise SystemExit(f"read_bench: {name}: a chunk failed verification")
+            check(out, data, cb, runs)
+            tout.fill_(0xA5)
+            _, cok, nw = c.read_tar(ctext, cofs, refs, files, sl, out=tout, verified=ver)
+            t = c.last_read_timings()
+            fms = c.last_frame_ms()
+            if not cok.all() or nw != total:
+                raise SystemExit(f"read_bench: {name}: tar read failed")
+            if i == 0:
+                check_tar(tout, data, cb, sl, names, offs, total)
+            if i >= args.warmup:
+                s_v.append(s["verify"])
+                s_g.append(s["gather"])
+                t_v.append(t["verify"])
+                t_g.append(t["gather"])
+                t_f.append(fms)
+        row = {"layout": name, "chunks": n, "chunk_bytes": cb, "files": int(len(sl)),
+               "payload_bytes": payload, "stream_bytes": total,
+               "header_padding_trailer_bytes": total - payload,
+               "tar_verify_ms_median": round(med(t_v), 4),
+               "tar_gather_ms_median": round(med(t_g), 4),
+               "tar_gather_ms_min_max": [round(min(t_g), 4), round(max(t_g), 4)],
+               "tar_frame_ms_median": round(med(t_f), 4),
+               "tar_frame_ms_min_max": [round(min(t_f), 4), round(max(t_f), 4)],
+               "read_slices_verify_ms_median": round(med(s_v), 4),
+               "read_slices_gather_ms_median": round(med(s_g), 4),
+               "read_slices_gather_ms_min_max": [round(min(s_g), 4), round(max(s_g), 4)],
+               "reps": args.reps, "warmup": args.warmup, "first_stream_checked": True}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del out, tout
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tar", action="store_true")
     ap.add_argument("--chunks", type=int, default=1024)
     ap.add_argument("--chunk-bytes", type=int, default=4 << 20)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r7", "read_path",
-                                                  "read_bench.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r8", "read_tar", "read_tar.json") if args.tar \
+            else os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("read_bench: needs a GPU")
     n, cb = args.chunks, args.chunk_bytes
@@ -85,9 +167,10 @@ def main():
     refs, _ = c.create_refs(data, cofs)  # Ref.Dek and Ref.Id of every chunk
     ctext = torch.empty_like(data)
     c.get_chunks(data, cofs, refs, out=ctext)  # XOR is its own inverse: the stored form
-    plain = torch.empty_like(data)
-    rows = []
-    for name, (sl, ver, runs) in layouts(n, cb, np.random.default_rng(7)).items():
+    rows = tar_rows(args, c, data, ctext, cofs, refs, n, cb) if args.tar else []
+    plain = None if args.tar else torch.empty_like(data)
+    for name, (sl, ver, runs) in ({} if args.tar else
+                                  layouts(n, cb, np.random.default_rng(7))).items():
         total = int(sl["size"].sum())
         out = torch.empty(total, dtype=torch.uint8, device="cuda:0")
         vms, gms, getms = [], [], []
@@ -124,7 +207,7 @@ def main():
     c.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
-        json.dump({"tool": "tools/read_bench.py", "device": torch.cuda.get_device_name(0),
+        json.dump({"tool": "tools/read_bench.py" + (" --tar" if args.tar else ""), "device": torch.cuda.get_device_name(0),
                    "layouts": rows}, f, indent=1)
         f.write("\n")
 
