@@ -676,6 +676,123 @@ int pfscdc_uw_create_group(pfscdc_group* g, int64_t mem_threshold,
                            const pfscdc_params* index_params, pfscdc_uw_cb cb, void* user,
                            pfscdc_uwriter** out);
 
+/* The unordered writer's chunk client: every chunk writer it makes from now on (the data
+ * writers and every index level of both indexes, with one or several group writers and over a
+ * device group) uploads its chunks' ciphertext into store (pfscdc_writer_set_store(w, store,
+ * 1)), so the filesets can be read back (pfscdc_index_read) after Close.  Call it before the
+ * first Put (PFSCDC_ESTATE afterwards); events, roots and Ref.Ids do not depend on it.  The
+ * store must outlive the writer; NULL turns the upload off again. */
+int pfscdc_uw_set_store(pfscdc_uwriter* w, pfscdc_store* store);
+
+/* ---- reading a fileset back (fileset/index/reader.go:41-181, fileset/merge.go:37-77) ------
+ * A fileset root (pfscdc_fileset_info.additive_root / deletive_root) is opened against the
+ * store the writer uploaded into: the index levels are read breadth-first, each level's chunks
+ * verified, decrypted and gathered by the read path into one device buffer, its pbutil frames
+ * (int64 LE length + index.Index proto, pbutil.go:39,65) walked and decoded on the device into
+ * the flat records below, which pfscdc_store_read_tar takes as they are. */
+
+/* index.WithRange / index.WithPrefix / the tag filter (index/option.go).  Each member may be
+ * NULL or "" (unset); a NULL filter selects everything.  atStart(name): name >= lower if lower
+ * is set, else name >= prefix.  atEnd(name): name > upper if upper is set, else the first
+ * min(len(name), len(prefix)) bytes of name > those of prefix (reader.go:95-122).  tag selects
+ * level-0 entries whose File.Tag equals it. */
+typedef struct pfscdc_index_filter {
+  const char* lower;
+  const char* upper;
+  const char* prefix;
+  const char* tag;
+} pfscdc_index_filter;
+
+#define PFSCDC_IDX_HAS_RANGE 1u     /* Index.Range is set (an entry of a level above 0) */
+#define PFSCDC_IDX_HAS_FILE 2u      /* Index.File is set */
+#define PFSCDC_IDX_HAS_CHUNK_REF 4u /* Range.ChunkRef is set: DataRef first + count of the list */
+
+/* One index.Index.  Strings lie in the list's blob, each followed by a NUL; absent proto3
+ * fields are zero / empty. */
+typedef struct pfscdc_index_entry {
+  uint64_t path_off;      /* Index.Path */
+  uint64_t tag_off;       /* File.Tag */
+  uint64_t last_path_off; /* Range.LastPath */
+  uint32_t path_len;
+  uint32_t tag_len;
+  uint32_t last_path_len;
+  uint32_t flags;         /* PFSCDC_IDX_* */
+  uint32_t first;         /* File.DataRefs = DataRefs [first, first + count) of the list */
+  uint32_t count;
+  int64_t size_bytes;     /* sum of the File's DataRef.SizeBytes */
+  int64_t range_offset;   /* Range.Offset */
+} pfscdc_index_entry;     /* 64 bytes */
+
+/* An owned list of entries in stream order: the entries, one packed blob of their strings and
+ * one pfscdc_full_dataref array.  pfscdc_index_list_tar_files gives one pfscdc_tar_file per
+ * entry (path into the blob, first, count), so that
+ *   pfscdc_store_read_tar(ctx, store, tar_files, count, datarefs, ndatarefs, ...)
+ * renders the list as a tar stream with no conversion.  Pointers stay valid until
+ * pfscdc_index_list_free. */
+typedef struct pfscdc_index_list pfscdc_index_list;
+uint32_t pfscdc_index_list_count(const pfscdc_index_list* l);
+const pfscdc_index_entry* pfscdc_index_list_entries(const pfscdc_index_list* l);
+const char* pfscdc_index_list_blob(const pfscdc_index_list* l, uint64_t* len);
+const pfscdc_full_dataref* pfscdc_index_list_datarefs(const pfscdc_index_list* l, uint32_t* n);
+const pfscdc_tar_file* pfscdc_index_list_tar_files(pfscdc_index_list* l);
+int pfscdc_index_list_free(pfscdc_index_list* l);
+
+/* The decode of one level's stream (n bytes of pbutil frames) on the host, with no GPU call:
+ * the specification the decode kernels are tested against, and the decode pfscdc_index_read
+ * uses when the PFSCDC_INDEX_DECODE knob is 0.  Every entry of the stream, unfiltered.
+ * PFSCDC_ECORRUPT for a stream that does not parse (a frame length that is negative or runs
+ * past the stream, a varint longer than 10 bytes, a nested length past its parent, a wire type
+ * that does not fit the field, an id, dek or hash that is not 32 bytes), with *err_offset
+ * (nullable) the offset of the first frame that does not; *out is then NULL.  Unknown fields of
+ * a known wire type are skipped.  Never reads outside [stream, stream + n). */
+int pfscdc_index_decode_host(const void* stream, uint64_t n, pfscdc_index_list** out,
+                             uint64_t* err_offset);
+/* Reader.Iterate's selection over a list of level-0 entries in path order: entries are taken
+ * from the first with atStart(path) up to the first with atEnd(path), those with another tag
+ * than filter->tag left out.  Host only. */
+int pfscdc_index_filter_list(const pfscdc_index_list* in, const pfscdc_index_filter* filter,
+                             pfscdc_index_list** out);
+/* index.NewReader(chunks, topIdx, opts...).Iterate (reader.go:41-83): the level-0 entries under
+ * root (an encoded index.Index) that the filter selects, in order.  A NULL or empty root gives
+ * an empty list; a root without a Range is itself a level-0 entry.  Levels are read breadth-
+ * first: of one level's entries, those with atStart(Range.LastPath) that precede the first with
+ * atEnd(Path) name the chunks of the level below, which are read whole (chunk.Reference: offset
+ * 0, Ref.SizeBytes) in one read-path call; the level's stream is the first chunk from its
+ * Range.Offset on followed by the later chunks whole (levelReader.setup / next).  The chunk of
+ * the entry the selection ends at (the first with atEnd(Path)) is read as well, as
+ * levelReader.next fetches it for the frame that runs on into it; no other chunk is read.
+ * Errors: PFSCDC_ENOTFOUND (a chunk id is not in the store), PFSCDC_ECORRUPT (a chunk fails
+ * verification, or a stream does not parse: pfscdc_last_error then names the level, counted
+ * from 0 for the stream the root names, and the offset in that level's stream of the first
+ * frame that does not parse); *out is then NULL and nothing was written past any array.
+ * The PFSCDC_INDEX_DECODE knob: 1 decodes on the device, 0 copies each level's bytes to the
+ * host and decodes them with pfscdc_index_decode_host; the lists are identical. */
+int pfscdc_index_read(pfscdc_ctx* ctx, const pfscdc_store* store, const void* root,
+                      uint64_t root_len, const pfscdc_index_filter* filter,
+                      pfscdc_index_list** out);
+/* Counts of the last pfscdc_index_read on ctx: out[0] index chunks read, out[1] chunks whose
+ * speculative frame walk was discarded and walked again from the chunk before's exit, out[2]
+ * levels read, out[3] frames decoded (all levels). */
+int pfscdc_last_index_stats(pfscdc_ctx* ctx, uint64_t out[4]);
+/* Its time (ms): out[0] the read path's verification and out[1] its decrypt-and-gather of the
+ * index chunks (device time, summed over the levels), out[2] the frame walk with its
+ * re-walks, out[3] the decode (device: count, prefix sums, fill; host arm: the host decode),
+ * out[4] the copy of the list (host arm: of the level's bytes) to the host; [2..4] wall time
+ * around synchronised stages. */
+int pfscdc_last_index_timings(pfscdc_ctx* ctx, float out[5]);
+
+/* MergeReader.iterate (merge.go:37-77) over stream.PriorityQueue (priority_queue.go:103-127):
+ * lists holds, for each of nfilesets filesets in order, its deletive list and then its additive
+ * list (2 * nfilesets pointers; NULL = an empty list), each in (path, tag) order.  Entries
+ * with equal (path, tag) form a group, groups come in path-then-tag order, and within a group
+ * the order is fileset 0 deletive, fileset 0 additive, fileset 1 deletive, ...  A group of one
+ * entry: deletive gives nothing, additive passes through.  A longer group: a deletive entry in
+ * last place drops the file, an earlier one clears the DataRefs collected so far, an additive
+ * one appends its DataRefs; the merged entry keeps the group's first entry's path and tag.
+ * Different tags of one path stay separate entries.  Host only. */
+int pfscdc_index_merge(const pfscdc_index_list* const* lists, uint32_t nfilesets,
+                       pfscdc_index_list** out);
+
 /* fileset.Clean(p, isDir) (fileset/util.go:67-77) into out (cap bytes incl. NUL). */
 int pfscdc_path_clean(const char* path, int is_directory, char* out, uint64_t cap);
 

@@ -65,6 +65,11 @@ EXPORTED = [
     "pfscdc_read_slices", "pfscdc_last_read_timings", "pfscdc_store_read",
     "pfscdc_tar_header", "pfscdc_tar_layout", "pfscdc_read_tar", "pfscdc_last_frame_ms",
     "pfscdc_store_read_tar",
+    "pfscdc_uw_set_store", "pfscdc_index_list_count", "pfscdc_index_list_entries",
+    "pfscdc_index_list_blob", "pfscdc_index_list_datarefs", "pfscdc_index_list_tar_files",
+    "pfscdc_index_list_free", "pfscdc_index_decode_host", "pfscdc_index_filter_list",
+    "pfscdc_index_read", "pfscdc_last_index_stats", "pfscdc_last_index_timings",
+    "pfscdc_index_merge",
 ]
 
 
@@ -113,6 +118,21 @@ def tar_files(files):
     return arr
 
 
+class IndexFilter(C.Structure):
+    _fields_ = [("lower", C.c_char_p), ("upper", C.c_char_p), ("prefix", C.c_char_p),
+                ("tag", C.c_char_p)]
+
+
+class IndexEntry(C.Structure):
+    _fields_ = [("path_off", C.c_uint64), ("tag_off", C.c_uint64), ("last_path_off", C.c_uint64),
+                ("path_len", C.c_uint32), ("tag_len", C.c_uint32), ("last_path_len", C.c_uint32),
+                ("flags", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32),
+                ("size_bytes", C.c_int64), ("range_offset", C.c_int64)]
+
+
+IDX_HAS_RANGE, IDX_HAS_FILE, IDX_HAS_CHUNK_REF = 1, 2, 4
+
+
 class AnnotationOut(C.Structure):
     _fields_ = [("user", C.c_uint64), ("has_data_ref", C.c_int32), ("reserved", C.c_int32),
                 ("data_ref", DataRef)]
@@ -134,6 +154,7 @@ class FilesetInfo(C.Structure):
 EV_CHUNK, EV_INDEX = 1, 2
 UW_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(UwEvent))
 
+assert C.sizeof(IndexEntry) == 64
 assert C.sizeof(Segment) == 56 and C.sizeof(Params) == 32 and C.sizeof(ChunkRef) == 96 and C.sizeof(FullDataRef) == 128
 
 WRITER_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(ChunkRef), C.POINTER(AnnotationOut),
@@ -306,6 +327,19 @@ def load() -> C.CDLL:
             "pfscdc_last_frame_ms": (i32, [vp, P(C.c_float)]),
             "pfscdc_store_read_tar": (i32, [vp, vp, P(TarFile), u32, P(FullDataRef), u32, u64,
                                             u64, vp, u64, i32, P(u64)]),
+            "pfscdc_uw_set_store": (i32, [vp, vp]),
+            "pfscdc_index_list_count": (u32, [vp]),
+            "pfscdc_index_list_entries": (P(IndexEntry), [vp]),
+            "pfscdc_index_list_blob": (vp, [vp, P(u64)]),
+            "pfscdc_index_list_datarefs": (P(FullDataRef), [vp, P(u32)]),
+            "pfscdc_index_list_tar_files": (P(TarFile), [vp]),
+            "pfscdc_index_list_free": (i32, [vp]),
+            "pfscdc_index_decode_host": (i32, [vp, u64, P(vp), P(u64)]),
+            "pfscdc_index_filter_list": (i32, [vp, P(IndexFilter), P(vp)]),
+            "pfscdc_index_read": (i32, [vp, vp, vp, u64, P(IndexFilter), P(vp)]),
+            "pfscdc_last_index_stats": (i32, [vp, P(u64)]),
+            "pfscdc_last_index_timings": (i32, [vp, P(C.c_float)]),
+            "pfscdc_index_merge": (i32, [P(vp), u32, P(vp)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

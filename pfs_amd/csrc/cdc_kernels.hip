@@ -32,6 +32,8 @@
 #include <algorithm>
 #include <type_traits>
 
+#define PFSCDC_HD __host__ __device__  // index_parse.h: the parser runs in the kernels
+#include "index_parse.h"
 #include "pfscdc_internal.h"
 
 #define PFS_DEV __device__ __forceinline__
@@ -2541,6 +2543,211 @@ hipError_t launch_rebase_files(pfscdc_segment* segs, uint64_t n, uint32_t base, 
   if (n == 0 || base == 0) return hipSuccess;
   const uint64_t blocks = std::min<uint64_t>((n + 255) / 256, 1024);
   rebase_files_kernel<<<(unsigned)blocks, 256, 0, st>>>(segs, n, base);
+  return hipGetLastError();
+}
+
+// ---- 8. index.Reader: one level's stream of pbutil frames into flat records -------------------
+// (fileset/index/reader.go:124-181 levelReader, pbutil/pbutil.go:39,65; parser: index_parse.h)
+//
+// 8a. Frame walk.  The frames are a chain (int64 LE length, proto, next length ...), so one
+// walker is serial; the level's chunks give the parallelism: every parent entry's Range.Offset
+// claims a frame start inside its chunk, and one wave walks from each claim to the first frame
+// start at or beyond the next chunk's begin (its exit), recording the starts on the way.  The
+// walks are speculative: index.cpp accepts chunk i + 1's walk only if chunk i's exit equals its
+// claim and launches the walk again from the exit otherwise.
+// One wave per walker: the wave stages kIdxWin bytes from the 16-byte line holding the current
+// position into LDS with one 16-byte load per lane and pass (1 KiB per wave instruction), then
+// lane 0 hops through the window in LDS (a hop is one dependent 8-byte read: ~64 cycles of LDS
+// latency against ~1-2 us for a dependent global load) until a length field crosses the
+// window's end.  A frame longer than the window is hopped over: the next window starts at the
+// next frame.  Every read lies in [0, n + 32) of a buffer allocated 64 bytes longer than n; a
+// length that is negative or reaches past n ends the walk with err = the frame's start.
+constexpr int kIdxWin = 8192;  // bytes staged per pass (+ 16: the window starts on a 16-B line)
+
+__global__ __launch_bounds__(64) void index_walk_kernel(
+    const uint8_t* __restrict__ buf, uint64_t n, const IdxWalk* __restrict__ walks, uint32_t nw,
+    uint64_t* __restrict__ starts, IdxWalkOut* __restrict__ out) {
+  __shared__ uint4 win[(kIdxWin + 16) / 16];
+  __shared__ uint64_t s_pos;
+  __shared__ uint32_t s_done;
+  const uint8_t* wb = (const uint8_t*)win;
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t i = blockIdx.x; i < nw; i += gridDim.x) {
+    const IdxWalk w = walks[i];
+    uint64_t pos = w.start, cnt = 0, err = kNone, past = 0;
+    if (pos == kNone) {
+      if (lane == 0) out[i] = IdxWalkOut{kNone, 0, kNone, 0};
+      continue;
+    }
+    for (;;) {  // pos, and the loop's exits, are uniform over the wave
+      if (pos >= w.limit) break;
+      if (pos + 8 > n) {  // bytes left, but not a length field
+        err = pos;
+        past = 1;
+        break;
+      }
+      const uint64_t base = pos & ~15ull;
+      // bytes [base, wend) are staged; wend <= n + 16 rounded: inside the padded allocation
+      const uint64_t wend = base + kIdxWin + 16 < n ? base + kIdxWin + 16 : ((n + 15) & ~15ull);
+      for (uint64_t t = base + 16ull * lane; t < wend; t += 16 * 64)
+        win[(t - base) >> 4] = *(const uint4*)(buf + t);
+      __syncthreads();
+      if (lane == 0) {
+        const uint64_t valid = wend < n ? wend : n;  // stream bytes in the window end here
+        uint64_t cur = pos;
+        uint32_t done = 0;
+        while (cur < w.limit) {
+          if (cur + 8 > valid) {
+            if (cur + 8 > n) {
+              err = cur;
+              past = 1;
+              done = 1;
+            }
+            break;  // stage again from cur
+          }
+          const int64_t len = idx_le64(wb + (cur - base));
+          if (len < 0 || (uint64_t)len > n - cur - 8 || cnt >= w.cap) {
+            err = cur;
+            past = len >= 0;
+            done = 1;
+            break;
+          }
+          starts[w.slot + cnt++] = cur;
+          cur += 8 + (uint64_t)len;
+        }
+        if (cur >= w.limit) done = 1;
+        s_pos = cur;
+        s_done = done;
+      }
+      __syncthreads();
+      pos = s_pos;
+      const uint32_t done = s_done;
+      __syncthreads();  // s_pos / win are rewritten by the next pass
+      if (done) break;
+    }
+    if (lane == 0) out[i] = IdxWalkOut{pos, cnt, err, past};
+  }
+}
+
+// 8b. Entry decode: a count pass (records and blob bytes per frame, every frame validated), the
+// prefix sums, and a fill pass that parses again and writes the entry record, the
+// pfscdc_full_datarefs and the strings at the frame's own ranges.  One frame per lane: frames
+// are ~250 bytes and independent, a level-0 stream of a large commit has 10^5..10^6 of them.
+// A frame that does not parse leaves {0, 0} and its start in *err_min (atomic min: the lowest
+// offending offset); index.cpp then never launches the fill.  The fill writes at most the
+// count pass's records (idx_parse's cap), so it stays inside its range whatever the bytes.
+constexpr int kIdxBlock = 256;
+
+__global__ __launch_bounds__(kIdxBlock) void index_count_kernel(
+    const uint8_t* __restrict__ buf, uint64_t n, const uint64_t* __restrict__ fstart, uint64_t nf,
+    IdxCount* __restrict__ cnt, unsigned long long* __restrict__ err_min) {
+  for (uint64_t f = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; f < nf;
+       f += (uint64_t)gridDim.x * kIdxBlock) {
+    const uint64_t s = fstart[f];
+    IdxCount c{0, 0};
+    bool ok = s + 8 <= n;
+    if (ok) {
+      const int64_t len = idx_le64(buf + s);
+      ok = len >= 0 && (uint64_t)len <= n - s - 8;
+      IdxFrame fr;
+      if (ok) ok = idx_parse(buf + s + 8, buf + s + 8 + len, &fr, nullptr, 0);
+      if (ok) ok = idx_blob_bytes(fr) <= 0xffffffffull;
+      if (ok) c = IdxCount{idx_records(fr), (uint32_t)idx_blob_bytes(fr)};
+    }
+    if (!ok) atomicMin(err_min, (unsigned long long)s);
+    cnt[f] = c;
+  }
+}
+
+// Exclusive prefix sums of both counts by one workgroup: tiles of 1,024 frames, a Hillis-Steele
+// scan in LDS per tile and the running totals carried in registers.  base[2 f] = records
+// before frame f, base[2 f + 1] = blob bytes before it; base[2 nf], base[2 nf + 1] the totals.
+constexpr int kIdxScanBlock = 1024;
+
+__global__ __launch_bounds__(kIdxScanBlock) void index_scan_kernel(
+    const IdxCount* __restrict__ cnt, uint64_t nf, uint64_t* __restrict__ base) {
+  __shared__ uint64_t a[kIdxScanBlock], b[kIdxScanBlock];
+  const uint32_t t = threadIdx.x;
+  uint64_t ca = 0, cb = 0;
+  for (uint64_t f0 = 0; f0 < nf; f0 += kIdxScanBlock) {
+    const uint64_t f = f0 + t;
+    const IdxCount c = f < nf ? cnt[f] : IdxCount{0, 0};
+    a[t] = c.ndr;
+    b[t] = c.blob;
+    __syncthreads();
+    for (uint32_t d = 1; d < kIdxScanBlock; d <<= 1) {
+      const uint64_t xa = t >= d ? a[t - d] : 0, xb = t >= d ? b[t - d] : 0;
+      __syncthreads();
+      a[t] += xa;
+      b[t] += xb;
+      __syncthreads();
+    }
+    if (f < nf) {
+      base[2 * f] = ca + a[t] - c.ndr;
+      base[2 * f + 1] = cb + b[t] - c.blob;
+    }
+    ca += a[kIdxScanBlock - 1];
+    cb += b[kIdxScanBlock - 1];
+    __syncthreads();
+  }
+  if (t == 0) {
+    base[2 * nf] = ca;
+    base[2 * nf + 1] = cb;
+  }
+}
+
+__global__ __launch_bounds__(kIdxBlock) void index_fill_kernel(
+    const uint8_t* __restrict__ buf, uint64_t n, const uint64_t* __restrict__ fstart, uint64_t nf,
+    const uint64_t* __restrict__ base, pfscdc_index_entry* __restrict__ entries,
+    pfscdc_full_dataref* __restrict__ drs, char* __restrict__ blob) {
+  for (uint64_t f = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; f < nf;
+       f += (uint64_t)gridDim.x * kIdxBlock) {
+    const uint64_t s = fstart[f];
+    const uint64_t first = base[2 * f], cap = base[2 * f + 2] - first;
+    const uint64_t at = base[2 * f + 1], room = base[2 * f + 3] - at;
+    if (s + 8 > n) continue;  // (the count pass refused such a frame: the fill is not launched)
+    const int64_t len = idx_le64(buf + s);
+    if (len < 0 || (uint64_t)len > n - s - 8) continue;
+    IdxFrame fr;
+    if (!idx_parse(buf + s + 8, buf + s + 8 + len, &fr, drs + first, cap)) continue;
+    if (idx_records(fr) != cap || idx_blob_bytes(fr) != room) continue;
+    idx_emit(fr, first, at, blob, &entries[f]);
+  }
+}
+
+// Launch widths: one wave per walker, one lane per frame, both up to 8 workgroups' worth of
+// waves per CU and capped by the PFSCDC_CHACHA_GRID knob like the gather's (the kernels stride).
+hipError_t launch_index_walk(const uint8_t* buf, uint64_t n, const IdxWalk* w, uint32_t nw,
+                             uint64_t* starts, IdxWalkOut* out, int num_cus, hipStream_t st) {
+  if (nw == 0) return hipSuccess;
+  const uint64_t full = (uint64_t)num_cus * 32;
+  index_walk_kernel<<<capped_grid(nw < full ? nw : full, Knob::ChachaGrid), 64, 0, st>>>(
+      buf, n, w, nw, starts, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_count(const uint8_t* buf, uint64_t n, const uint64_t* fstart, uint64_t nf,
+                              IdxCount* cnt, unsigned long long* err_min, int num_cus,
+                              hipStream_t st) {
+  if (nf == 0) return hipSuccess;
+  const uint64_t need = (nf + kIdxBlock - 1) / kIdxBlock, full = (uint64_t)num_cus * 8;
+  index_count_kernel<<<capped_grid(need < full ? need : full, Knob::ChachaGrid), kIdxBlock, 0,
+                       st>>>(buf, n, fstart, nf, cnt, err_min);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_scan(const IdxCount* cnt, uint64_t nf, uint64_t* base, hipStream_t st) {
+  index_scan_kernel<<<1, kIdxScanBlock, 0, st>>>(cnt, nf, base);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_fill(const uint8_t* buf, uint64_t n, const uint64_t* fstart, uint64_t nf,
+                             const uint64_t* base, pfscdc_index_entry* entries,
+                             pfscdc_full_dataref* drs, char* blob, int num_cus, hipStream_t st) {
+  if (nf == 0) return hipSuccess;
+  const uint64_t need = (nf + kIdxBlock - 1) / kIdxBlock, full = (uint64_t)num_cus * 8;
+  index_fill_kernel<<<capped_grid(need < full ? need : full, Knob::ChachaGrid), kIdxBlock, 0,
+                      st>>>(buf, n, fstart, nf, base, entries, drs, blob);
   return hipGetLastError();
 }
 

@@ -265,6 +265,7 @@ struct Streams {  // the ctxs of every chunk stream kind; events out
   std::map<int64_t, pfscdc_ctx*> index_ctx;  // by seed (= level)
   pfscdc_uw_cb cb = nullptr;
   void* user = nullptr;
+  pfscdc_store* const* store = nullptr;  // the writer's chunk client (pfscdc_uw_set_store)
   std::mutex* emit_mu = nullptr;  // events of concurrent group writers reach cb one at a time
   // several group writers: a group's events are held here (the index frames copied) and
   // released in group order once the groups before it have emitted theirs
@@ -283,6 +284,10 @@ struct Streams {  // the ctxs of every chunk stream kind; events out
     std::unique_lock<std::mutex> lk;
     if (emit_mu) lk = std::unique_lock<std::mutex>(*emit_mu);
     return cb(user, &ev) != 0 ? PFSCDC_ECALLBACK : PFSCDC_OK;
+  }
+  // a new chunk writer of this stream set uploads into the store, when there is one
+  int attach(pfscdc_writer* cw) const {
+    return store && *store ? pfscdc_writer_set_store(cw, *store, 1) : PFSCDC_OK;
   }
   pfscdc_ctx* level_ctx(int level) {
     auto it = index_ctx.find(level);
@@ -336,6 +341,7 @@ struct IndexWriter {  // index/writer.go:27-162
     l->iw = this;
     l->level = k;
     int rc = pfscdc_writer_create(c, &IndexWriter::callback, l.get(), 0, &l->cw);
+    if (!rc) rc = st->attach(l->cw);
     if (rc) return rc;
     levels.push_back(std::move(l));
     return PFSCDC_OK;
@@ -437,7 +443,10 @@ struct FilesetWriter {  // fileset/writer.go:21-182
     if (cw) pfscdc_writer_destroy(cw);
   }
 
-  int open() { return pfscdc_writer_create(st->data_ctx, &FilesetWriter::callback, this, 0, &cw); }
+  int open() {
+    int rc = pfscdc_writer_create(st->data_ctx, &FilesetWriter::callback, this, 0, &cw);
+    return rc ? rc : st->attach(cw);
+  }
 
   static int check_path(const IndexT* prev, const IndexT* idx) {
     if (!prev) return PFSCDC_OK;
@@ -814,6 +823,8 @@ struct pfscdc_uwriter {  // unordered_writer.go:15-26
   std::vector<std::pair<std::vector<std::pair<std::string, std::string>>,
                         std::vector<std::pair<std::string, std::string>>>> keys;  // files, deletes
   uint32_t next_fileset = 0;
+  pfscdc_store* store = nullptr;  // pfscdc_uw_set_store: every chunk writer uploads into it
+  bool started = false;           // a Put or Delete was made
   bool closed = false;
   int err = 0;
   std::string errmsg;  // pfscdc_uw_last_error
@@ -1120,6 +1131,7 @@ int pfscdc_uw_create_group(pfscdc_group* g, int64_t mem_threshold,
     gw->st.cb = cb;
     gw->st.user = user;
     gw->st.emit_mu = &w->emit_mu;
+    gw->st.store = &w->store;
     gw->st.index_params = ip;
     gw->st.data_ctx = pfscdc_group_ctx(g, k);
     gw->device = pfscdc::ctx_device(gw->st.data_ctx);
@@ -1148,6 +1160,7 @@ int pfscdc_uw_create(pfscdc_ctx* data_ctx, int64_t mem_threshold,
     gw->st.cb = cb;
     gw->st.user = user;
     gw->st.emit_mu = &w->emit_mu;
+    gw->st.store = &w->store;
     gw->st.index_params = ip;
     if (k == 0) {
       gw->st.data_ctx = data_ctx;
@@ -1174,6 +1187,7 @@ int pfscdc_uw_put(pfscdc_uwriter* w, const char* path, const char* tag, int appe
   if (!w || !path || (n && !data)) return PFSCDC_EINVAL;
   if (w->err) return w->err;
   if (w->closed) return w->fail(PFSCDC_ESTATE, "Put after Close");
+  w->started = true;
   int rc = w->put(path, tag ? tag : "", append_file != 0, (const uint8_t*)data, n);
   return rc ? w->fail(rc, "Put") : PFSCDC_OK;
 }
@@ -1182,8 +1196,16 @@ int pfscdc_uw_delete(pfscdc_uwriter* w, const char* path, const char* tag) {
   if (!w || !path) return PFSCDC_EINVAL;
   if (w->err) return w->err;
   if (w->closed) return w->fail(PFSCDC_ESTATE, "Delete after Close");
+  w->started = true;
   int rc = w->del(path, tag ? tag : "");
   return rc ? w->fail(rc, "Delete") : PFSCDC_OK;
+}
+
+int pfscdc_uw_set_store(pfscdc_uwriter* w, pfscdc_store* store) {
+  if (!w) return PFSCDC_EINVAL;
+  if (w->started || w->closed) return PFSCDC_ESTATE;  // before the first Put
+  w->store = store;
+  return PFSCDC_OK;
 }
 
 int pfscdc_uw_close(pfscdc_uwriter* w) {

@@ -1,0 +1,324 @@
+// index.cpp — reading a fileset back: index.Reader.Iterate over a chunk store and
+// MergeReader.iterate (host logic; the frame walk and entry decode kernels are in
+// cdc_kernels.hip, the proto parser both sides share in index_parse.h).
+//
+// Reference (paths under /root/reference/src/internal):
+//   storage/fileset/index/reader.go:41-83    Iterate: levels, atEnd / atStart / tag
+//   storage/fileset/index/reader.go:95-122   atStart, atEnd (range and prefix filters)
+//   storage/fileset/index/reader.go:124-181  levelReader: chunk[Offset:], then whole chunks
+//   storage/fileset/merge.go:37-77,157-164   MergeReader.iterate, compare (path, then tag)
+//   stream/priority_queue.go:103-127         groups of equal streams, sorted by priority
+//   pbutil/pbutil.go:39,65                   int64 LE length + proto
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "index_list.h"
+#include "pfscdc_internal.h"
+
+namespace {
+
+using namespace pfscdc;
+using List = pfscdc_index_list;
+
+// Reader.Iterate's walk over one level's entries: the level-0 entries the filter selects go to
+// sel, the Range entries whose chunks hold the level below to parents.  *tail: the Range entry
+// the walk ended at (the first with atEnd(Path)), or -1.  Its chunk is read too, as
+// levelReader.next fetches it whatever its path when a frame runs on into it: the last wanted
+// frame may end there, and a wanted entry may even begin there (an entry that begins on the
+// chunk's border with the path of the entry before it, another tag, is not the one the chunk's
+// Range names).  Nothing wanted begins after it.  false: an entry that cannot be followed (why
+// set).
+bool select(const List& l, const IdxFilter& f, std::vector<uint32_t>* sel,
+            std::vector<uint32_t>* parents, int64_t* tail, const char** why) {
+  bool leaf = false, range = false;
+  *tail = -1;
+  for (uint32_t i = 0; i < l.entries.size(); i++) {
+    const pfscdc_index_entry& e = l.entries[i];
+    if (f.at_end(idx_path(l, e))) {
+      if ((e.flags & PFSCDC_IDX_HAS_RANGE) && (e.flags & PFSCDC_IDX_HAS_CHUNK_REF)) *tail = i;
+      break;
+    }
+    if (!(e.flags & PFSCDC_IDX_HAS_RANGE)) {
+      leaf = true;
+      if (f.at_start(idx_path(l, e)) && f.tag_ok(idx_tag(l, e))) sel->push_back(i);
+    } else {
+      range = true;
+      if (!(e.flags & PFSCDC_IDX_HAS_CHUNK_REF)) {
+        *why = "a Range without a chunk_ref";
+        return false;
+      }
+      if (f.at_start(idx_last_path(l, e))) parents->push_back(i);
+    }
+  }
+  if (leaf && range) {
+    *why = "Range entries and level-0 entries in one level";
+    return false;
+  }
+  return true;
+}
+
+struct DevMem {  // hipMalloc'ed for the call
+  void* p = nullptr;
+  ~DevMem() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+  template <class T>
+  T* as() const { return (T*)p; }
+};
+
+using Clock = std::chrono::steady_clock;
+float ms_since(Clock::time_point t0) {
+  return std::chrono::duration<float, std::milli>(Clock::now() - t0).count();
+}
+
+#define IDX_HIP(ctx, expr)                                                             \
+  do {                                                                                 \
+    hipError_t e_ = (expr);                                                            \
+    if (e_ != hipSuccess)                                                              \
+      return pfscdc::ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PFSCDC_ENOMEM : PFSCDC_EHIP, \
+                              std::string(#expr) + ": " + hipGetErrorString(e_));      \
+  } while (0)
+
+int corrupt(pfscdc_ctx* ctx, uint32_t level, uint64_t offset) {
+  return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT,
+                          "index level " + std::to_string(level) + ": the frame at stream offset " +
+                              std::to_string(offset) + " does not parse");
+}
+
+// One level's stream, already on the device (d_buf[0, n), allocated 64 bytes longer; chunk i < nc
+// is [cb[i], cb[i + 1]) and claims the frame start cb[i] + off[i]), walked and decoded into out.
+// open_end: the selection ends before the level does (its last chunk is the tail chunk).
+int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, uint64_t n,
+                        const std::vector<uint64_t>& cb, const std::vector<int64_t>& off,
+                        uint32_t nc, bool open_end, List* out) {
+  IndexStats& st = ctx_index_stats(ctx);
+  hipStream_t s = ctx_stream(ctx);
+  const int cus = ctx_num_cus(ctx);
+  const uint64_t start0 = cb[0] + (uint64_t)off[0];
+  auto t0 = Clock::now();
+  // ---- the frame walk: one speculative walker per chunk, settled along the chain
+  std::vector<IdxWalk> walks(nc);
+  for (uint32_t i = 0; i < nc; i++) {
+    const uint64_t len = cb[i + 1] - cb[i];
+    const bool claim = off[i] >= 0 && (uint64_t)off[i] <= len;
+    walks[i] = IdxWalk{claim ? cb[i] + (uint64_t)off[i] : kIdxNone, cb[i + 1], cb[i] / 8 + i,
+                       len / 8 + 1};
+  }
+  DevMem d_walks, d_outs, d_starts;
+  IDX_HIP(ctx, d_walks.alloc(sizeof(IdxWalk) * nc));
+  IDX_HIP(ctx, d_outs.alloc(sizeof(IdxWalkOut) * nc));
+  IDX_HIP(ctx, d_starts.alloc(sizeof(uint64_t) * (n / 8 + nc + 1)));
+  IDX_HIP(ctx, hipMemcpyAsync(d_walks.p, walks.data(), sizeof(IdxWalk) * nc, hipMemcpyHostToDevice, s));
+  IDX_HIP(ctx, launch_index_walk(d_buf, n, d_walks.as<IdxWalk>(), nc, d_starts.as<uint64_t>(),
+                                 d_outs.as<IdxWalkOut>(), cus, s));
+  std::vector<IdxWalkOut> outs(nc);
+  IDX_HIP(ctx, hipMemcpyAsync(outs.data(), d_outs.p, sizeof(IdxWalkOut) * nc, hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipStreamSynchronize(s));
+  // The truth is the chain from chunk 0's claim: chunk i's walk stands only if the chunk
+  // before is settled and its exit is chunk i's claim.  A chunk wholly inside one entry (its
+  // one annotation gets Offset 0, index/writer.go:102-121) holds no frame start at all; any
+  // other chunk with a wrong claim is walked again from the exit.  Each repeat settles a chunk.
+  uint64_t nf = 0;
+  for (uint32_t i = 0; i < nc; i++) {
+    if (i > 0 && walks[i].start != outs[i - 1].exit) {
+      st.n[1]++;
+      const uint64_t from = outs[i - 1].exit;
+      if (from >= cb[i + 1]) {
+        outs[i] = IdxWalkOut{from, 0, kIdxNone, 0};
+      } else {
+        walks[i].start = from;
+        IDX_HIP(ctx, hipMemcpyAsync(d_walks.as<IdxWalk>() + i, &walks[i], sizeof(IdxWalk),
+                                    hipMemcpyHostToDevice, s));
+        IDX_HIP(ctx, launch_index_walk(d_buf, n, d_walks.as<IdxWalk>() + i, 1,
+                                       d_starts.as<uint64_t>(), d_outs.as<IdxWalkOut>() + i, cus, s));
+        IDX_HIP(ctx, hipMemcpyAsync(&outs[i], d_outs.as<IdxWalkOut>() + i, sizeof(IdxWalkOut),
+                                    hipMemcpyDeviceToHost, s));
+        IDX_HIP(ctx, hipStreamSynchronize(s));
+      }
+    }
+    nf += outs[i].count;
+    if (outs[i].err != kIdxNone) {
+      // A frame that runs past a selection that ends before the level does is past the filter's
+      // end (a wanted frame ends inside the tail chunk): the stream ends in front of it.
+      if (!(open_end && outs[i].past)) return corrupt(ctx, level, outs[i].err - start0);
+      for (uint32_t k = i + 1; k < nc; k++) outs[k] = IdxWalkOut{n, 0, kIdxNone, 0};
+      break;
+    }
+  }
+  st.ms[2] += ms_since(t0);
+  st.n[3] += nf;
+  if (nf == 0) return PFSCDC_OK;
+  if (nf > 0xffffffffull) return ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "more than 2^32 index entries");
+  // ---- the decode: frame starts packed, count pass, prefix sums, fill pass
+  t0 = Clock::now();
+  DevMem d_fstart, d_cnt, d_base, d_err;
+  IDX_HIP(ctx, d_fstart.alloc(sizeof(uint64_t) * nf));
+  IDX_HIP(ctx, d_cnt.alloc(sizeof(IdxCount) * nf));
+  IDX_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 2 * (nf + 1)));
+  IDX_HIP(ctx, d_err.alloc(sizeof(uint64_t)));
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < nc; at += outs[i].count, i++)
+    if (outs[i].count)
+      IDX_HIP(ctx, hipMemcpyAsync(d_fstart.as<uint64_t>() + at, d_starts.as<uint64_t>() + walks[i].slot,
+                                  sizeof(uint64_t) * outs[i].count, hipMemcpyDeviceToDevice, s));
+  uint64_t h_err = kIdxNone, totals[2] = {0, 0};
+  IDX_HIP(ctx, hipMemcpyAsync(d_err.p, &h_err, sizeof h_err, hipMemcpyHostToDevice, s));
+  IDX_HIP(ctx, launch_index_count(d_buf, n, d_fstart.as<uint64_t>(), nf, d_cnt.as<IdxCount>(),
+                                  d_err.as<unsigned long long>(), cus, s));
+  IDX_HIP(ctx, launch_index_scan(d_cnt.as<IdxCount>(), nf, d_base.as<uint64_t>(), s));
+  IDX_HIP(ctx, hipMemcpyAsync(&h_err, d_err.p, sizeof h_err, hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 2 * nf, sizeof totals,
+                              hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipStreamSynchronize(s));
+  if (h_err != kIdxNone) return corrupt(ctx, level, h_err - start0);
+  if (totals[0] > 0xffffffffull) return ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "more than 2^32 DataRefs");
+  DevMem d_entries, d_drs, d_blob;
+  IDX_HIP(ctx, d_entries.alloc(sizeof(pfscdc_index_entry) * nf));
+  IDX_HIP(ctx, d_drs.alloc(sizeof(pfscdc_full_dataref) * totals[0]));
+  IDX_HIP(ctx, d_blob.alloc(totals[1]));
+  IDX_HIP(ctx, launch_index_fill(d_buf, n, d_fstart.as<uint64_t>(), nf, d_base.as<uint64_t>(),
+                                 d_entries.as<pfscdc_index_entry>(),
+                                 d_drs.as<pfscdc_full_dataref>(), d_blob.as<char>(), cus, s));
+  IDX_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[3] += ms_since(t0);
+  // ---- the list to the host
+  t0 = Clock::now();
+  out->entries.resize(nf);
+  out->drs.resize(totals[0]);
+  out->blob.resize(totals[1]);
+  IDX_HIP(ctx, hipMemcpyAsync(out->entries.data(), d_entries.p, sizeof(pfscdc_index_entry) * nf,
+                              hipMemcpyDeviceToHost, s));
+  if (totals[0])
+    IDX_HIP(ctx, hipMemcpyAsync(out->drs.data(), d_drs.p, sizeof(pfscdc_full_dataref) * totals[0],
+                                hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipMemcpyAsync(out->blob.data(), d_blob.p, totals[1], hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[4] += ms_since(t0);
+  return PFSCDC_OK;
+}
+
+// The level below the entries parents of cur: their chunks through the read path into one
+// device buffer, then the decode (device, or host with the PFSCDC_INDEX_DECODE knob at 0).
+int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const List& cur,
+               std::vector<uint32_t> parents, int64_t tail, List* out) {
+  IndexStats& st = ctx_index_stats(ctx);
+  if (tail >= 0) parents.push_back((uint32_t)tail);
+  const uint32_t nc = (uint32_t)parents.size();
+  std::vector<pfscdc_full_dataref> refs(nc);
+  std::vector<uint64_t> cb(nc + 1, 0);
+  std::vector<int64_t> off(nc);
+  for (uint32_t i = 0; i < nc; i++) {
+    const pfscdc_index_entry& e = cur.entries[parents[i]];
+    refs[i] = cur.drs[e.first + e.count];
+    off[i] = e.range_offset;
+    if (refs[i].data.size_bytes < 0 || cb[i] + (uint64_t)refs[i].data.size_bytes < cb[i])
+      return ctx_fail(ctx, PFSCDC_ECORRUPT, "index level " + std::to_string(level) +
+                                                ": a Range's chunk_ref has a bad size");
+    cb[i + 1] = cb[i] + (uint64_t)refs[i].data.size_bytes;
+  }
+  const uint64_t n = cb[nc];
+  // levelReader.setup: the first chunk from Range.Offset on (Go panics on an offset beyond it)
+  if (off[0] < 0 || (uint64_t)off[0] > cb[1])
+    return ctx_fail(ctx, PFSCDC_ECORRUPT, "index level " + std::to_string(level) +
+                                              ": Range.Offset beyond its chunk");
+  IDX_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  DevMem d_buf;
+  IDX_HIP(ctx, d_buf.alloc(n + 64));
+  uint64_t nw = 0;
+  int rc = pfscdc_store_read(ctx, store, refs.data(), nc, d_buf.p, n, 1, &nw);
+  if (rc == PFSCDC_ENOTFOUND)
+    return ctx_fail(ctx, rc,
+                    "index level " + std::to_string(level) + ": a chunk id is not in the store");
+  if (rc == PFSCDC_EINVAL)
+    return ctx_fail(ctx, PFSCDC_ECORRUPT, "index level " + std::to_string(level) +
+                                              ": a Range's chunk_ref reaches past its chunk");
+  if (rc) return rc;
+  float rt[2] = {0.f, 0.f};
+  (void)pfscdc_last_read_timings(ctx, rt);
+  st.ms[0] += rt[0];
+  st.ms[1] += rt[1];
+  st.n[0] += nc;
+  st.n[2]++;
+  if (knob(Knob::IndexDecode) != 0)
+    return decode_level_device(ctx, level, d_buf.as<uint8_t>(), n, cb, off, nc, tail >= 0, out);
+  // the host arm: the level's bytes to the host, then the specification's decode
+  const uint64_t start0 = (uint64_t)off[0];
+  auto t0 = Clock::now();
+  std::vector<uint8_t> h(n - start0);
+  if (!h.empty())
+    IDX_HIP(ctx, hipMemcpy(h.data(), d_buf.as<uint8_t>() + start0, h.size(), hipMemcpyDeviceToHost));
+  st.ms[4] += ms_since(t0);
+  t0 = Clock::now();
+  uint64_t err = kIdxNone;
+  rc = idx_decode_stream(h.data(), h.size(), h.size(), tail >= 0, out, &err);
+  st.ms[3] += ms_since(t0);
+  st.n[3] += out->entries.size();
+  if (rc == PFSCDC_ECORRUPT) return corrupt(ctx, level, err);
+  return rc ? ctx_fail(ctx, rc, "more than 2^32 index records") : PFSCDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfscdc_index_read(pfscdc_ctx* ctx, const pfscdc_store* store, const void* root,
+                      uint64_t root_len, const pfscdc_index_filter* filter,
+                      pfscdc_index_list** out) {
+  if (!ctx || !store || !out) return PFSCDC_EINVAL;
+  *out = nullptr;
+  pfscdc::ctx_index_stats(ctx) = pfscdc::IndexStats();
+  std::unique_ptr<List> result(new List());
+  if (!root || !root_len) {  // r.topIdx == nil
+    *out = result.release();
+    return PFSCDC_OK;
+  }
+  const IdxFilter f(filter);
+  // topLevel(): the root as a stream of one entry
+  std::unique_ptr<List> cur(new List());
+  {
+    const uint8_t *b = (const uint8_t*)root, *e = b + root_len;
+    IdxFrame fr;
+    if (!pfscdc::idx_parse(b, e, &fr, nullptr, 0) || !idx_append_frame(cur.get(), fr, b, e))
+      return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT, "the root index does not parse");
+  }
+  for (uint32_t level = 0;; level++) {
+    std::vector<uint32_t> sel, parents;
+    int64_t tail = -1;
+    const char* why = nullptr;
+    if (!select(*cur, f, &sel, &parents, &tail, &why))
+      return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT,
+                              "index level " + std::to_string(level) + " (its parent): " + why);
+    if (!sel.empty()) {
+      if (sel.size() == cur->entries.size() && result->entries.empty())
+        result.swap(cur);  // everything selected: the decoded list is the result
+      else
+        for (uint32_t i : sel) idx_append_entry(result.get(), *cur, cur->entries[i]);
+    }
+    if (parents.empty()) break;
+    if (level >= 64) return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT, "more than 64 index levels");
+    std::unique_ptr<List> next(new List());
+    if (int rc = read_level(ctx, store, level, *cur, parents, tail, next.get())) return rc;
+    cur.swap(next);
+  }
+  *out = result.release();
+  return PFSCDC_OK;
+}
+
+int pfscdc_last_index_stats(pfscdc_ctx* ctx, uint64_t out[4]) {
+  if (!ctx || !out) return PFSCDC_EINVAL;
+  std::memcpy(out, pfscdc::ctx_index_stats(ctx).n, sizeof(uint64_t) * 4);
+  return PFSCDC_OK;
+}
+
+int pfscdc_last_index_timings(pfscdc_ctx* ctx, float out[5]) {
+  if (!ctx || !out) return PFSCDC_EINVAL;
+  std::memcpy(out, pfscdc::ctx_index_stats(ctx).ms, sizeof(float) * 5);
+  return PFSCDC_OK;
+}
+
+}  // extern "C"

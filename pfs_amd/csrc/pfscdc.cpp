@@ -168,10 +168,13 @@ struct pfscdc_ctx {
   uint64_t nsegs = 0;
   const uint8_t* dev_data = nullptr;  // data pointer of the last scan
   pfscdc_ctx* hash_after = nullptr;   // pfscdc_order_hash_after
+  IndexStats index_stats;             // the last pfscdc_index_read
 };
 
 namespace pfscdc {
 const pfscdc_params& ctx_params(const pfscdc_ctx* ctx) { return ctx->params; }
+IndexStats& ctx_index_stats(pfscdc_ctx* ctx) { return ctx->index_stats; }
+int ctx_num_cus(const pfscdc_ctx* ctx) { return ctx->num_cus; }
 }  // namespace pfscdc
 
 namespace {

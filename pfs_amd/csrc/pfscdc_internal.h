@@ -47,7 +47,7 @@ enum class Knob : int {
   HashBinBytes, HashWaves, HashFair, HashFairEvery,
   RefIdSplit, CommitTwoSets, CommitLongPct,
   UwWorkers, UwInflight, UwMirror, UwIndexGrouped, UwArenaPoolBytes, CtxCache, CopyThreads,
-  Trace,
+  IndexDecode, Trace,
   kCount
 };
 int64_t knob(Knob k);
@@ -269,6 +269,44 @@ int read_slices_impl(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes, int ct
 // segs[i].file += base for i < n (a device group's gathered index: member-local file ids
 // become the commit's)
 hipError_t launch_rebase_files(pfscdc_segment* segs, uint64_t n, uint32_t base, hipStream_t st);
+// ---- index.Reader on the device (index.cpp; kernels in cdc_kernels.hip) ----
+// One frame walker: hop from start (kNone: no walk) length by length until the first frame
+// start at or beyond limit; the starts go to starts[slot, slot + cap).
+struct IdxWalk {
+  uint64_t start, limit, slot, cap;
+};
+struct IdxWalkOut {
+  uint64_t exit;   // first frame start >= limit (where the walk stopped, with err)
+  uint64_t count;  // frame starts recorded
+  uint64_t err;    // kNone, or the start of the frame whose length does not fit the stream
+  uint64_t past;   // with err: 1 the frame (or its length field) runs past the stream's end,
+                   // 0 a negative length
+};
+struct IdxCount {  // per frame: records in the DataRef array, bytes in the blob
+  uint32_t ndr, blob;
+};
+// walkers w[0, nw) over the stream buf[0, n) (buf 16-B aligned, readable to n + 32)
+hipError_t launch_index_walk(const uint8_t* buf, uint64_t n, const IdxWalk* w, uint32_t nw,
+                             uint64_t* starts, IdxWalkOut* out, int num_cus, hipStream_t st);
+// count pass over the nf frames at fstart[]: cnt[f]; *err_min = the lowest start of a frame
+// that does not parse (preset to kNone)
+hipError_t launch_index_count(const uint8_t* buf, uint64_t n, const uint64_t* fstart, uint64_t nf,
+                              IdxCount* cnt, unsigned long long* err_min, int num_cus,
+                              hipStream_t st);
+// exclusive prefix sums of cnt[0, nf) into base[0, nf] ({records, blob bytes} per frame)
+hipError_t launch_index_scan(const IdxCount* cnt, uint64_t nf, uint64_t* base, hipStream_t st);
+// fill pass: entries[f], drs[base[2f], base[2f + 2)), blob[base[2f + 1], base[2f + 3))
+hipError_t launch_index_fill(const uint8_t* buf, uint64_t n, const uint64_t* fstart, uint64_t nf,
+                             const uint64_t* base, pfscdc_index_entry* entries,
+                             pfscdc_full_dataref* drs, char* blob, int num_cus, hipStream_t st);
+// what pfscdc_last_index_stats / pfscdc_last_index_timings report
+struct IndexStats {
+  uint64_t n[4] = {};
+  float ms[5] = {};
+};
+IndexStats& ctx_index_stats(pfscdc_ctx* ctx);
+int ctx_num_cus(const pfscdc_ctx* ctx);
+
 hipError_t launch_synth(uint8_t* out, const uint64_t* offs, uint32_t nfiles, const uint32_t* ids,
                         const uint64_t* starts, uint64_t seed, uint32_t mode, hipStream_t st);
 

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -147,6 +148,7 @@ struct ChunkFormer {
 
 struct pfscdc_store {
   std::map<std::string, std::string> objects;  // Ref.Id -> ciphertext
+  std::mutex mu;  // uploads: an unordered writer's group writers share one store
 };
 
 struct pfscdc_writer {
@@ -252,10 +254,14 @@ int callbacks(pfscdc_writer* w) {
 int upload(pfscdc_store* st, const pfscdc_ref& ref, const uint8_t* ct, uint64_t begin,
            uint64_t end) {
   std::string id((const char*)ref.id, 32);
-  if (st->objects.count(id)) return PFSCDC_OK;
+  {
+    std::lock_guard<std::mutex> lk(st->mu);
+    if (st->objects.count(id)) return PFSCDC_OK;
+  }
   std::string obj(end - begin, '\0');
   if (!obj.empty() && hipMemcpy(&obj[0], ct + begin, obj.size(), hipMemcpyDeviceToHost) != hipSuccess)
     return PFSCDC_EHIP;
+  std::lock_guard<std::mutex> lk(st->mu);
   st->objects.emplace(std::move(id), std::move(obj));
   return PFSCDC_OK;
 }
@@ -969,6 +975,7 @@ int pfscdc_store_destroy(pfscdc_store* s) {
 
 int pfscdc_store_put(pfscdc_store* s, const uint8_t id[32], const void* ctext, uint64_t n) {
   if (!s || !id || (n && !ctext)) return PFSCDC_EINVAL;
+  std::lock_guard<std::mutex> lk(s->mu);
   s->objects.emplace(std::string((const char*)id, 32), std::string((const char*)ctext, n));
   return PFSCDC_OK;
 }

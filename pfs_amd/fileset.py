@@ -203,22 +203,264 @@ class TarStream:
             c.close()
 
 
+@dataclass
+class FileEntry:
+    """One level-0 index entry: a file (or one tag of it) with its DataRefs."""
+    path: str
+    tag: str
+    size_bytes: int
+    data_refs: list
+
+
+def _filter(lower, upper, prefix, tag):
+    """pfscdc_index_filter of the four optional strings (None when all are unset)."""
+    vals = [v.encode() if isinstance(v, str) else v for v in (lower, upper, prefix, tag)]
+    if not any(vals):
+        return None
+    return _lib.IndexFilter(*[v or None for v in vals])
+
+
+class IndexList:
+    """An owned pfscdc_index_list: entries in stream order over one string blob and one
+    pfscdc_full_dataref array."""
+
+    def __init__(self, ptr):
+        self.lib = _lib.load()
+        self._p = ptr
+
+    def __len__(self) -> int:
+        return self.lib.pfscdc_index_list_count(self._p)
+
+    def _views(self):
+        n = len(self)
+        ents = self.lib.pfscdc_index_list_entries(self._p)
+        blen, ndr = C.c_uint64(), C.c_uint32()
+        bp = self.lib.pfscdc_index_list_blob(self._p, C.byref(blen))
+        blob = C.string_at(bp, blen.value) if blen.value else b""
+        drs = self.lib.pfscdc_index_list_datarefs(self._p, C.byref(ndr))
+        return n, ents, blob, drs, ndr.value
+
+    @staticmethod
+    def _dataref(d):
+        from .chunk import DataRef, Ref
+        return DataRef(Ref(d.ref_size, bool(d.edge), -1, bytes(d.ref.id), bytes(d.ref.dek)),
+                       bytes(d.data.hash), d.data.offset_bytes, d.data.size_bytes)
+
+    def raw(self) -> list:
+        """Every entry as a dict of all its fields (paths and tags as bytes)."""
+        n, ents, blob, drs, _ = self._views()
+        out = []
+        for i in range(n):
+            e = ents[i]
+            d = {"path": blob[e.path_off:e.path_off + e.path_len],
+                 "tag": blob[e.tag_off:e.tag_off + e.tag_len],
+                 "has_file": bool(e.flags & _lib.IDX_HAS_FILE),
+                 "size_bytes": e.size_bytes,
+                 "data_refs": [self._dataref(drs[k]) for k in range(e.first, e.first + e.count)],
+                 "range": None}
+            if e.flags & _lib.IDX_HAS_RANGE:
+                ref = self._dataref(drs[e.first + e.count]) \
+                    if e.flags & _lib.IDX_HAS_CHUNK_REF else None
+                d["range"] = (e.range_offset,
+                              blob[e.last_path_off:e.last_path_off + e.last_path_len], ref)
+            out.append(d)
+        return out
+
+    def files(self) -> list:
+        return [FileEntry(d["path"].decode("utf-8", "surrogateescape"),
+                          d["tag"].decode("utf-8", "surrogateescape"), d["size_bytes"],
+                          d["data_refs"]) for d in self.raw()]
+
+    def free(self) -> None:
+        if getattr(self, "_p", None):
+            self.lib.pfscdc_index_list_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def index_decode_host(stream: bytes) -> IndexList:
+    """pfscdc_index_decode_host: every entry of one level's stream of pbutil frames, decoded on
+    the host.  PfsCdcError(PFSCDC_ECORRUPT) names the offset of the frame that does not parse."""
+    out, err = C.c_void_p(), C.c_uint64()
+    rc = _lib.load().pfscdc_index_decode_host(stream, len(stream), C.byref(out), C.byref(err))
+    if rc:
+        raise _lib.PfsCdcError(rc, f"index stream does not parse at offset {err.value}")
+    return IndexList(out)
+
+
+def index_filter(lst: IndexList, lower=None, upper=None, prefix=None, tag=None) -> IndexList:
+    """Reader.Iterate's selection over a level-0 list (pfscdc_index_filter_list)."""
+    f = _filter(lower, upper, prefix, tag)
+    out = C.c_void_p()
+    rc = _lib.load().pfscdc_index_filter_list(lst._p, C.byref(f) if f is not None else None,
+                                              C.byref(out))
+    if rc:
+        raise _lib.PfsCdcError(rc, "pfscdc_index_filter_list")
+    return IndexList(out)
+
+
+def index_merge(pairs) -> IndexList:
+    """MergeReader.iterate over (deletive list, additive list) pairs in fileset order
+    (pfscdc_index_merge); None stands for an empty list."""
+    pairs = list(pairs)
+    arr = (C.c_void_p * max(1, 2 * len(pairs)))()
+    for i, (d, a) in enumerate(pairs):
+        arr[2 * i] = d._p if d is not None else None
+        arr[2 * i + 1] = a._p if a is not None else None
+    out = C.c_void_p()
+    rc = _lib.load().pfscdc_index_merge(arr, len(pairs), C.byref(out))
+    if rc:
+        raise _lib.PfsCdcError(rc, "pfscdc_index_merge")
+    return IndexList(out)
+
+
+def index_read(chunker, store, root: Optional[bytes], lower=None, upper=None, prefix=None,
+               tag=None) -> IndexList:
+    """index.NewReader(chunks, root, opts...).Iterate on ``chunker``'s context
+    (pfscdc_index_read): the level-0 entries under ``root`` that the filter selects.  KeyError
+    for a chunk missing from the store, PfsCdcError(PFSCDC_ECORRUPT) for a chunk that fails
+    verification or a level that does not parse."""
+    f = _filter(lower, upper, prefix, tag)
+    out = C.c_void_p()
+    rc = chunker.lib.pfscdc_index_read(chunker.ctx, store._s, root, len(root) if root else 0,
+                                       C.byref(f) if f is not None else None, C.byref(out))
+    if rc:
+        msg = chunker.lib.pfscdc_last_error(chunker.ctx)
+        msg = msg.decode() if msg else ""
+        if rc == _lib.PFSCDC_ENOTFOUND:
+            raise KeyError(msg or "chunk not in the store")
+        raise _lib.PfsCdcError(rc, f"index read: {msg}")
+    return IndexList(out)
+
+
+def last_index_stats(chunker) -> dict:
+    """Counts and stage times (ms) of the last index_read on ``chunker``'s context."""
+    n, ms = (C.c_uint64 * 4)(), (C.c_float * 5)()
+    chunker.lib.pfscdc_last_index_stats(chunker.ctx, n)
+    chunker.lib.pfscdc_last_index_timings(chunker.ctx, ms)
+    out = dict(zip(["chunks_read", "rewalked_chunks", "levels", "frames"], [int(x) for x in n]))
+    out.update(zip(["verify_ms", "gather_ms", "walk_ms", "decode_ms", "d2h_ms"],
+                   [round(float(x), 4) for x in ms]))
+    return out
+
+
+class _FlatRefs:
+    """The DataRefs of an IndexList as TarStream looks at them: their count, and their Ref
+    ids when a missing chunk has to be named."""
+
+    def __init__(self, lst: IndexList):
+        self._l = lst
+
+    def __len__(self) -> int:
+        return self._l._views()[4]
+
+    def __iter__(self):
+        _, _, _, drs, n = self._l._views()
+        return (IndexList._dataref(drs[k]) for k in range(n))
+
+
+class _ListTarStream(TarStream):
+    """TarStream over a merged IndexList: the list's own pfscdc_tar_file and
+    pfscdc_full_dataref arrays go to pfscdc_store_read_tar as they are."""
+
+    def __init__(self, storage, lst: IndexList):
+        self._list = lst
+        self.device = storage.device
+        self._store = storage.store
+        n, ents, blob, drs, ndr = lst._views()
+        lib = lst.lib
+        self._tf = lib.pfscdc_index_list_tar_files(lst._p)
+        sizes = (C.c_uint64 * max(1, n))(*[ents[i].size_bytes for i in range(n)])
+        offs, total = (C.c_uint64 * (n + 1))(), C.c_uint64()
+        rc = lib.pfscdc_tar_layout(self._tf, n, sizes, offs, C.byref(total))
+        if rc:
+            for i in range(n):  # name the first file that cannot be written
+                e = ents[i]
+                tar_header(blob[e.path_off:e.path_off + e.path_len].decode("utf-8", "replace"),
+                           e.size_bytes)
+            raise ValueError("tar: a directory entry with DataRefs")
+        self.entry_offsets, self._total = list(offs), total.value
+        self._c = (self._tf, n, drs, _FlatRefs(lst))
+
+    def _arrays(self):
+        if self._store is None:
+            raise ValueError("the storage has no chunk store to read from")
+        return self._c
+
+
+class FileSet:
+    """The merged view of opened filesets (``Storage.open``): the files that
+    ``MergeReader.iterate`` yields, in path-then-tag order."""
+
+    def __init__(self, storage, merged: IndexList):
+        self._storage, self._list = storage, merged
+
+    def files(self) -> list:
+        """``FileEntry`` (path, tag, size, DataRefs) per merged file."""
+        return self._list.files()
+
+    def read(self, path: str) -> bytes:
+        """The content of ``path``: its entries' DataRefs in tag order, through the chunk
+        read path (pfscdc_store_read).  KeyError if the fileset has no such file."""
+        from .chunk import Storage as ChunkStorage
+        drs = [d for f in self.files() if f.path == path for d in f.data_refs]
+        if not any(f.path == path for f in self.files()):
+            raise KeyError(path)
+        return ChunkStorage(self._storage.device, store=self._storage.store).new_reader(drs).get()
+
+    def tar(self) -> TarStream:
+        """``GetFileTAR`` over the merged files (a ``TarStream``)."""
+        return _ListTarStream(self._storage, self._list)
+
+
 class Storage:
-    """``fileset.Storage`` restricted to the write path, bound to one GPU, or with
-    ``devices`` to a device group (one process, several GPUs: pfscdc_uw_create_group deals
-    the serialized filesets over them; the filesets and events equal one GPU's)."""
+    """``fileset.Storage`` restricted to the write path and to reading filesets back, bound to
+    one GPU, or with ``devices`` to a device group (one process, several GPUs:
+    pfscdc_uw_create_group deals the serialized filesets over them; the filesets and events
+    equal one GPU's).  ``store``: the chunk client; with one, every chunk the unordered writers
+    form (data and index) is uploaded into it and ``open`` reads filesets back from it."""
 
     def __init__(self, device: int = 0, params: ChunkParams = ChunkParams(),
                  mem_threshold: int = DEFAULT_MEMORY_THRESHOLD,
                  index_params: Optional[ChunkParams] = None,
-                 devices: Optional[Sequence[int]] = None):
+                 devices: Optional[Sequence[int]] = None, store=None):
         self.device, self.params = device, params
         self.devices = list(devices) if devices is not None else None
         self.mem_threshold, self.index_params = mem_threshold, index_params
+        self.store = store
         self._idle: list = []  # data-stream contexts (or groups) of closed writers, for the next
 
     def new_unordered_writer(self) -> "UnorderedWriter":
         return UnorderedWriter(self)
+
+    def open(self, filesets, lower=None, upper=None, prefix=None, tag=None) -> FileSet:
+        """The merged view of ``filesets`` (the ``Primitive`` infos ``UnorderedWriter.close()``
+        returns, (additive root, deletive root) pairs, or bare additive roots), in order:
+        both indexes of every fileset are read with the filter (index.Reader over the store)
+        and merged (MergeReader.iterate)."""
+        if self.store is None:
+            raise ValueError("the storage has no chunk store to read from")
+        roots = []
+        for fs in filesets:
+            if isinstance(fs, (bytes, bytearray)) or fs is None:
+                roots.append((fs, None))
+            elif isinstance(fs, tuple):
+                roots.append(fs)
+            else:
+                roots.append((fs.additive, fs.deletive))
+        c = Chunker(ChunkParams(), self.device)
+        try:
+            pairs = [(index_read(c, self.store, d, lower, upper, prefix, tag),
+                      index_read(c, self.store, a, lower, upper, prefix, tag))
+                     for a, d in roots]
+        finally:
+            c.close()
+        return FileSet(self, index_merge(pairs))
 
     def _take_chunker(self):
         # a context (stream, events, device staging) per GPU, reused writer after writer, as
@@ -282,6 +524,10 @@ class UnorderedWriter:
         if rc:
             raise _lib.PfsCdcError(rc, "pfscdc_uw_create")
         self._w = w
+        if getattr(storage, "store", None) is not None:
+            rc = self.lib.pfscdc_uw_set_store(w, storage.store._s)
+            if rc:
+                raise _lib.PfsCdcError(rc, "pfscdc_uw_set_store")
 
     def _on_event(self, _user, ev_p) -> int:
         try:

@@ -20,7 +20,17 @@ The first tar stream of each layout is checked: every file's content against the
 sampled headers against pfscdc_tar_header, padding and trailer zero.  Writes
 profiles/r8/read_tar/read_tar.json.
 
-usage: python tools/read_bench.py [--tar] [--chunks N] [--chunk-bytes B] [--reps R]
+--index: reading a fileset back (pfscdc_index_read).  Two commits are written through the
+unordered writer into a store at the reference's index parameters, 65,536 files of 4 KiB and
+1,048,576 files of 256 B, and the additive root of each is read back with the device decode
+(PFSCDC_INDEX_DECODE=1) and the host decode (0), the arms alternating call by call.  Per arm:
+median, min and max of the call's wall time and of its stages (read-path verification and
+gather of the index chunks, frame walk with the re-walk count, decode, copy to the host).
+Every list is compared, array for array, with pfscdc_index_decode_host over the writer's own
+level-0 index events, and its first and last 500 entries with the events decoded by the protobuf
+runtime.  Writes profiles/r9/index_read/index_read.json.
+
+usage: python tools/read_bench.py [--tar | --index] [--chunks N] [--chunk-bytes B] [--reps R]
                                   [--warmup W] [--out PATH]"""
 import argparse
 import json
@@ -145,8 +155,83 @@ def tar_rows(args, c, data, ctext, cofs, refs, n, cb):
     return rows
 
 
+def list_arrays(lst):
+    """The three arrays of an IndexList as bytes."""
+    import ctypes as C
+    n, ents, _, drs, ndr = lst._views()
+    blen = C.c_uint64()
+    bp = lst.lib.pfscdc_index_list_blob(lst._p, C.byref(blen))
+    return (C.string_at(ents, 64 * n) if n else b"", C.string_at(bp, blen.value) if blen.value else b"",
+            C.string_at(drs, 128 * ndr) if ndr else b"")
+
+
+def index_rows(args):
+    import time
+
+    from oracle import fileset as OF
+    from pfs_amd import chunk as pc
+    from pfs_amd import fileset as PF
+    rows = []
+    for nfiles, fbytes in ((65536, 4096), (1 << 20, 256)):
+        store = pc.ChunkStore()
+        st = PF.Storage(0, ChunkParams(), store=store)
+        w = st.new_unordered_writer()
+        data = np.random.default_rng(nfiles).integers(0, 256, nfiles * fbytes + 64, dtype=np.uint8)
+        t0 = time.perf_counter()
+        for i in range(nfiles):
+            w.put("/bench/d%03d/f%07d" % (i >> 12, i), "", False, data[i * fbytes:(i + 1) * fbytes])
+        infos = w.close()
+        write_s = time.perf_counter() - t0
+        frames = [e[2] for e in w.events[0] if e[0] == "index" and e[1] == 0]
+        index_chunks = sum(1 for e in w.events[0] if e[0] == "chunk" and e[1] == 0)
+        w.release()
+        assert len(infos) == 1 and len(frames) == nfiles
+        want = list_arrays(PF.index_decode_host(b"".join(frames)))
+        M = OF._msgs()["Index"]
+        c = Chunker(ChunkParams(), 0)
+        keys = ["verify_ms", "gather_ms", "walk_ms", "decode_ms", "d2h_ms"]
+        runs = {1: [], 0: []}
+        for i in range(args.warmup + args.reps):
+            for arm in (1, 0):
+                _lib.set_knob("PFSCDC_INDEX_DECODE", arm)
+                t0 = time.perf_counter()
+                lst = PF.index_read(c, store, infos[0].additive)
+                wall = (time.perf_counter() - t0) * 1e3
+                stats = PF.last_index_stats(c)
+                if list_arrays(lst) != want:
+                    raise SystemExit("read_bench: the list differs from the writer's events")
+                if i == 0:
+                    raw = lst.raw()
+                    for k in list(range(500)) + list(range(nfiles - 500, nfiles)):
+                        m = M.FromString(frames[k][8:])
+                        got = raw[k]
+                        if (got["path"], got["tag"]) != (m.path.encode(), m.file.tag.encode()) or \
+                                [(d.ref.id, d.hash, d.offset_bytes, d.size_bytes) for d in got["data_refs"]] != \
+                                [(d.ref.id, d.hash, d.offset_bytes, d.size_bytes) for d in m.file.data_refs]:
+                            raise SystemExit(f"read_bench: entry {k} differs from its event")
+                lst.free()
+                if i >= args.warmup:
+                    stats["wall_ms"] = wall
+                    runs[arm].append(stats)
+        _lib.set_knob("PFSCDC_INDEX_DECODE", 1)
+        c.close()
+        row = {"files": nfiles, "file_bytes": fbytes, "index_stream_bytes": sum(map(len, frames)),
+               "index_chunks_all_levels": index_chunks, "write_s": round(write_s, 2),
+               "reps": args.reps, "warmup": args.warmup, "lists_equal_events": True}
+        for arm, name in ((1, "device"), (0, "host")):
+            r = runs[arm]
+            row[name] = {k: {"median": round(statistics.median(x[k] for x in r), 3),
+                             "min": round(min(x[k] for x in r), 3),
+                             "max": round(max(x[k] for x in r), 3)} for k in keys + ["wall_ms"]}
+            row[name].update({k: r[0][k] for k in ("chunks_read", "rewalked_chunks", "levels", "frames")})
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--index", action="store_true")
     ap.add_argument("--tar", action="store_true")
     ap.add_argument("--chunks", type=int, default=1024)
     ap.add_argument("--chunk-bytes", type=int, default=4 << 20)
@@ -159,6 +244,16 @@ def main():
             else os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("read_bench: needs a GPU")
+    if args.index:
+        if args.out == os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json"):
+            args.out = os.path.join(ROOT, "profiles", "r9", "index_read", "index_read.json")
+        rows = index_rows(args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/read_bench.py --index", "device": torch.cuda.get_device_name(0),
+                       "shapes": rows}, f, indent=1)
+            f.write("\n")
+        return
     n, cb = args.chunks, args.chunk_bytes
     c = Chunker(ChunkParams(), 0)
     cofs = np.arange(n + 1, dtype=np.uint64) * np.uint64(cb)
