@@ -792,6 +792,80 @@ int pfscdc_last_index_timings(pfscdc_ctx* ctx, float out[5]);
  * Different tags of one path stay separate entries.  Host only. */
 int pfscdc_index_merge(const pfscdc_index_list* const* lists, uint32_t nfilesets,
                        pfscdc_index_list** out);
+/* MergeReader.iterateDeletive (merge.go:79-94): lists holds the deletive list of each of
+ * nfilesets filesets (nfilesets pointers; NULL = an empty list).  Entries with equal (path, tag)
+ * form a group, and each group yields its first entry (the lowest fileset's) as it is.  Host
+ * only: the specification of PFSCDC_MERGE_DELETIVE. */
+int pfscdc_index_merge_deletive(const pfscdc_index_list* const* lists, uint32_t nfilesets,
+                                pfscdc_index_list** out);
+#define PFSCDC_MERGE_FILES 0    /* MergeReader.iterate: lists as pfscdc_index_merge takes them */
+#define PFSCDC_MERGE_DELETIVE 1 /* MergeReader.iterateDeletive: nfilesets deletive lists */
+/* Either merge on ctx.  The PFSCDC_INDEX_MERGE knob: 1 merges on the device (the streams are
+ * uploaded, every entry is ranked by binary searches in the other streams, the groups are formed
+ * and counted, and the merged entries, strings and DataRefs are written at prefix-summed
+ * ranges), 0 calls the host function of the mode; the lists are identical, array for array.
+ * The device arm hands a call to the host arm in two cases only: a list that is not strictly
+ * ascending in (path, tag), and more than 2^32 - 1 entries or DataRef records in the input. */
+int pfscdc_index_merge_ctx(pfscdc_ctx* ctx, int mode, const pfscdc_index_list* const* lists,
+                           uint32_t nfilesets, pfscdc_index_list** out);
+/* The last pfscdc_index_merge_ctx on ctx: out[0] 1 the device arm ran, 0 the host arm; out[1]
+ * entries in; out[2] groups (device arm; 0 from the host arm); out[3] entries out. */
+int pfscdc_last_merge_stats(pfscdc_ctx* ctx, uint64_t out[4]);
+/* Its time (ms, wall time around synchronised stages): out[0] the upload of the lists, out[1]
+ * rank, grouping and prefix sums (host arm: the whole host merge), out[2] the emit (entries,
+ * strings, DataRef copy), out[3] the copy of the list to the host. */
+int pfscdc_last_merge_timings(pfscdc_ctx* ctx, float out[4]);
+
+/* shard (fileset/shard.go:27-49) over a merged list: cb receives each shard's path range
+ * (lower, upper; "" = an open end).  A range is closed in front of the first file that finds
+ * threshold or more content bytes collected (the test comes before the file is added); its upper
+ * is the last file's path and the next lower is that next file's path; the last upper is "".  An
+ * empty (or NULL) list gives one open range.  A path whose tags lie on both sides of a border is
+ * in both ranges, as in the reference.  A non-zero return of cb ends the walk with
+ * PFSCDC_ECALLBACK.  Host only. */
+typedef int (*pfscdc_shard_cb)(void* user, const char* lower, const char* upper);
+int pfscdc_shard(const pfscdc_index_list* files, int64_t threshold, pfscdc_shard_cb cb, void* user);
+
+/* ---- fileset.Writer with Delete and Copy (fileset/writer.go:77-125,151-182), for Compact and
+ * Concat (fileset/compaction.go:43-57, storage.go:226-238) --------------------------------------
+ * Storage.newWriter: one fileset written in path order.  data_ctx must have PFSCDC_OPT_REF_IDS;
+ * store (not NULL) is the chunk client: Copy reads chunks from it, new data and index chunks are
+ * uploaded into it.  index_params as for pfscdc_uw_create.  Events are the unordered writer's,
+ * with fileset 0; a chunk passed through by reference arrives as a PFSCDC_EV_CHUNK with
+ * chunk.copied = 1.  Errors are sticky and named by pfscdc_fsw_last_error.
+ *   Storage.Compact: create, one pfscdc_fsw_copy_filesets over all inputs (the task's path
+ *     range as the filter), close.
+ *   Storage.Concat: create, one pfscdc_fsw_copy_filesets per input in order (each input's paths
+ *     after the one before's, or checkPath refuses them), close. */
+typedef struct pfscdc_fswriter pfscdc_fswriter;
+int pfscdc_fsw_create(pfscdc_ctx* data_ctx, const pfscdc_params* index_params, pfscdc_store* store,
+                      pfscdc_uw_cb cb, void* user, pfscdc_fswriter** out);
+/* Writer.Delete (writer.go:77-90).  PFSCDC_EINVAL (checkPath): the same (path, tag) as the
+ * Delete before, or a path below its path. */
+int pfscdc_fsw_delete(pfscdc_fswriter* w, const char* path, const char* tag);
+/* Writer.Copy (writer.go:105-125): a fresh Index{Path, File{Tag}} through checkPath (against the
+ * Copy before: PFSCDC_EINVAL as above) and Annotate, then per DataRef sizeBytes += SizeBytes and
+ * pfscdc_writer_copy.  PFSCDC_ENOTFOUND: a chunk that has to be read is not in the store;
+ * PFSCDC_ECORRUPT: it fails verification. */
+int pfscdc_fsw_copy(pfscdc_fswriter* w, const char* path, const char* tag,
+                    const pfscdc_full_dataref* drs, uint32_t n);
+/* CopyFiles(ctx, w, fs, true) (util.go:27-40) over the two lists of an opened fileset: every
+ * deletive entry as a Delete, then every additive entry as a Copy.  The Copies go in runs, each
+ * prefetched together (pfscdc_writer_prefetch over the run's DataRefs); a run ends once the
+ * chunks it will re-roll hold 256 MiB, and their plaintext is dropped after the run.  Either
+ * list may be NULL (empty). */
+int pfscdc_fsw_copy_lists(pfscdc_fswriter* w, const pfscdc_index_list* additive,
+                          const pfscdc_index_list* deletive);
+/* Storage.Open(ids, opts...) (storage.go:111-128) and CopyFiles: both roots of every fileset are
+ * read with the filter (pfscdc_index_read), merged in both modes (pfscdc_index_merge_ctx) and
+ * copied (pfscdc_fsw_copy_lists).  One fileset is read with no merge; none copies nothing. */
+int pfscdc_fsw_copy_filesets(pfscdc_fswriter* w, const pfscdc_fileset_info* filesets, uint32_t n,
+                             const pfscdc_index_filter* filter);
+int pfscdc_fsw_close(pfscdc_fswriter* w); /* Writer.Close (writer.go:151-182) */
+/* The Primitive of the closed writer; the roots stay valid until pfscdc_fsw_destroy. */
+int pfscdc_fsw_fileset(const pfscdc_fswriter* w, pfscdc_fileset_info* out);
+const char* pfscdc_fsw_last_error(const pfscdc_fswriter* w);
+int pfscdc_fsw_destroy(pfscdc_fswriter* w);
 
 /* fileset.Clean(p, isDir) (fileset/util.go:67-77) into out (cap bytes incl. NUL). */
 int pfscdc_path_clean(const char* path, int is_directory, char* out, uint64_t cap);

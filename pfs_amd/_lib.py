@@ -69,7 +69,11 @@ EXPORTED = [
     "pfscdc_index_list_blob", "pfscdc_index_list_datarefs", "pfscdc_index_list_tar_files",
     "pfscdc_index_list_free", "pfscdc_index_decode_host", "pfscdc_index_filter_list",
     "pfscdc_index_read", "pfscdc_last_index_stats", "pfscdc_last_index_timings",
-    "pfscdc_index_merge",
+    "pfscdc_index_merge", "pfscdc_index_merge_deletive", "pfscdc_index_merge_ctx",
+    "pfscdc_last_merge_stats", "pfscdc_last_merge_timings", "pfscdc_shard",
+    "pfscdc_fsw_create", "pfscdc_fsw_delete", "pfscdc_fsw_copy", "pfscdc_fsw_copy_lists",
+    "pfscdc_fsw_copy_filesets", "pfscdc_fsw_close", "pfscdc_fsw_fileset",
+    "pfscdc_fsw_last_error", "pfscdc_fsw_destroy",
 ]
 
 
@@ -152,6 +156,8 @@ class FilesetInfo(C.Structure):
 
 
 EV_CHUNK, EV_INDEX = 1, 2
+MERGE_FILES, MERGE_DELETIVE = 0, 1
+SHARD_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_char_p)
 UW_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(UwEvent))
 
 assert C.sizeof(IndexEntry) == 64
@@ -340,6 +346,20 @@ def load() -> C.CDLL:
             "pfscdc_last_index_stats": (i32, [vp, P(u64)]),
             "pfscdc_last_index_timings": (i32, [vp, P(C.c_float)]),
             "pfscdc_index_merge": (i32, [P(vp), u32, P(vp)]),
+            "pfscdc_index_merge_deletive": (i32, [P(vp), u32, P(vp)]),
+            "pfscdc_index_merge_ctx": (i32, [vp, i32, P(vp), u32, P(vp)]),
+            "pfscdc_last_merge_stats": (i32, [vp, P(u64)]),
+            "pfscdc_last_merge_timings": (i32, [vp, P(C.c_float)]),
+            "pfscdc_shard": (i32, [vp, i64, SHARD_CB, vp]),
+            "pfscdc_fsw_create": (i32, [vp, P(Params), vp, UW_CB, vp, P(vp)]),
+            "pfscdc_fsw_delete": (i32, [vp, C.c_char_p, C.c_char_p]),
+            "pfscdc_fsw_copy": (i32, [vp, C.c_char_p, C.c_char_p, P(FullDataRef), u32]),
+            "pfscdc_fsw_copy_lists": (i32, [vp, vp, vp]),
+            "pfscdc_fsw_copy_filesets": (i32, [vp, P(FilesetInfo), u32, P(IndexFilter)]),
+            "pfscdc_fsw_close": (i32, [vp]),
+            "pfscdc_fsw_fileset": (i32, [vp, P(FilesetInfo)]),
+            "pfscdc_fsw_last_error": (C.c_char_p, [vp]),
+            "pfscdc_fsw_destroy": (i32, [vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

@@ -2751,4 +2751,294 @@ hipError_t launch_index_fill(const uint8_t* buf, uint64_t n, const uint64_t* fst
   return hipGetLastError();
 }
 
+// ---- 9. MergeReader: the index lists of several filesets merged into one ----------------------
+// (fileset/merge.go:37-94 iterate / iterateDeletive, :157-164 compare;
+// stream/priority_queue.go:103-127: groups of equal keys, ordered by stream)
+//
+// The streams lie concatenated stream-major (MrgIn).  Every stream is strictly ascending in
+// (path, tag), so an entry's place in the merged order is a sum of binary searches:
+//   rank(e of stream s at index i) = i + sum_{t > s} lower_bound_t(key e) + sum_{t < s} upper_bound_t(key e)
+// which orders equal keys by stream number, the PriorityQueue's order.  Keys compare as
+// strings.Compare: unsigned bytes, a proper prefix first, the path and then the tag.
+// 9a rank: one lane per entry, one compare against its predecessor (a stream out of order sets
+//    *bad: the ranks are then no permutation and index.cpp hands the call to the host arm).
+// 9b group: one lane per merged position; a position whose key differs from its predecessor's
+//    is a head, walks its group (at most one entry per stream) and leaves what it emits.
+// 9c scan: index_scan_kernel's shape with three running sums (entries, records, blob bytes).
+// 9d fill: one lane per emitting head writes the entry, its strings, and one MrgCopy per
+//    contributing source entry; it walks the group as 9b did and writes nothing unless its
+//    counts equal the ranges the prefix sums gave it.
+// 9e copy: the DataRefs (128 B each, the bulk of the bytes) in 16-byte pieces, 8 neighbouring
+//    lanes per source entry.
+struct MrgKey {
+  const uint8_t *p, *t;
+  uint32_t pn, tn;
+};
+
+__device__ inline uint32_t mrg_stream(const MrgIn& in, uint64_t g) {
+  // the last s with stream_begin[s] <= g (stream_begin[0] = 0, stream_begin[ns] = n > g)
+  uint32_t lo = 0, hi = in.ns;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (in.stream_begin[mid] <= g) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__device__ inline MrgKey mrg_key(const MrgIn& in, uint64_t g, uint32_t s) {
+  const pfscdc_index_entry& e = in.entries[g];
+  const uint8_t* b = (const uint8_t*)in.blob + in.blob_base[s];
+  return MrgKey{b + e.path_off, b + e.tag_off, e.path_len, e.tag_len};
+}
+
+__device__ inline int mrg_cmp_str(const uint8_t* a, uint32_t an, const uint8_t* b, uint32_t bn) {
+  const uint32_t k = an < bn ? an : bn;
+  for (uint32_t i = 0; i < k; i++)
+    if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+  return an < bn ? -1 : an > bn ? 1 : 0;
+}
+
+__device__ inline int mrg_cmp(const MrgKey& a, const MrgKey& b) {
+  const int c = mrg_cmp_str(a.p, a.pn, b.p, b.pn);
+  return c ? c : mrg_cmp_str(a.t, a.tn, b.t, b.tn);
+}
+
+__global__ __launch_bounds__(kIdxBlock) void merge_rank_kernel(MrgIn in,
+                                                               uint32_t* __restrict__ order,
+                                                               uint32_t* __restrict__ bad) {
+  for (uint64_t g = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; g < in.n;
+       g += (uint64_t)gridDim.x * kIdxBlock) {
+    const uint32_t s = mrg_stream(in, g);
+    const MrgKey key = mrg_key(in, g, s);
+    uint64_t rank = g - in.stream_begin[s];
+    if (rank > 0 && mrg_cmp(mrg_key(in, g - 1, s), key) >= 0) atomicOr(bad, 1u);
+    for (uint32_t t = 0; t < in.ns; t++) {
+      if (t == s) continue;
+      const uint64_t b = in.stream_begin[t];
+      uint64_t lo = b, hi = in.stream_begin[t + 1];
+      while (lo < hi) {  // t > s: the entries below key; t < s: those not above it
+        const uint64_t mid = lo + (hi - lo) / 2;
+        const int c = mrg_cmp(mrg_key(in, mid, t), key);
+        if (t > s ? c < 0 : c <= 0) lo = mid + 1;
+        else hi = mid;
+      }
+      rank += lo - b;
+    }
+    order[rank] = (uint32_t)g;  // rank < n whatever the streams hold: every term is a count
+  }
+}
+
+struct MrgGroup {
+  uint32_t emit, merged;
+  uint64_t recs, blob;
+  int64_t size;
+};
+
+// The group that begins at merged position p.  copy (nullable): the MrgCopy of every source
+// entry whose DataRefs the group keeps, laid out from record first on, written only if the
+// group's records are cap in all (what the count pass found).
+__device__ inline MrgGroup mrg_walk(const MrgIn& in, const uint32_t* __restrict__ order, uint64_t p,
+                                    MrgCopy* __restrict__ copy, uint64_t first, uint64_t cap) {
+  const uint64_t g0 = order[p];
+  const uint32_t s0 = mrg_stream(in, g0);
+  const pfscdc_index_entry& e0 = in.entries[g0];
+  const MrgKey k0 = mrg_key(in, g0, s0);
+  const bool files = in.mode == PFSCDC_MERGE_FILES;  // stream 2k: fileset k's deletive list
+  uint64_t q = p + 1, from = (files && s0 % 2 == 0) ? p + 1 : p;  // members [from, q) are kept
+  for (; q < in.n; q++) {
+    const uint64_t g = order[q];
+    const uint32_t s = mrg_stream(in, g);
+    if (mrg_cmp(mrg_key(in, g, s), k0) != 0) break;
+    if (files && s % 2 == 0) from = q + 1;
+  }
+  MrgGroup r{0, 0, 0, 0, 0};
+  r.blob = (uint64_t)e0.path_len + e0.tag_len + e0.last_path_len + 3;
+  if (!files || q - p == 1) {  // the first entry as it is (iterate: a lone deletive entry: nothing)
+    if (files && s0 % 2 == 0) return r;
+    r.emit = 1;
+    r.recs = (uint64_t)e0.count + ((e0.flags & PFSCDC_IDX_HAS_CHUNK_REF) ? 1u : 0u);
+    r.size = e0.size_bytes;
+    if (copy && r.recs && r.recs == cap)
+      copy[g0] = MrgCopy{(uint32_t)first, (uint32_t)r.recs, (uint32_t)(in.dr_base[s0] + e0.first), 0};
+    return r;
+  }
+  if (from == q) return r;  // a deletive entry in last place drops the file
+  r.emit = r.merged = 1;
+  uint64_t size = 0;
+  for (uint64_t m = from; m < q; m++) {
+    const pfscdc_index_entry& e = in.entries[order[m]];
+    r.recs += e.count;
+    size += (uint64_t)e.size_bytes;  // an entry's size_bytes is its File DataRefs' wrapping sum
+  }
+  r.size = (int64_t)size;
+  if (copy && r.recs == cap) {
+    uint64_t at = first;
+    for (uint64_t m = from; m < q; m++) {
+      const uint64_t g = order[m];
+      const pfscdc_index_entry& e = in.entries[g];
+      if (e.count)
+        copy[g] = MrgCopy{(uint32_t)at, e.count, (uint32_t)(in.dr_base[mrg_stream(in, g)] + e.first), 0};
+      at += e.count;
+    }
+  }
+  return r;
+}
+
+__global__ __launch_bounds__(kIdxBlock) void merge_group_kernel(MrgIn in,
+                                                                const uint32_t* __restrict__ order,
+                                                                MrgCount* __restrict__ cnt,
+                                                                unsigned long long* __restrict__ heads) {
+  unsigned long long mine = 0;
+  for (uint64_t p = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; p < in.n;
+       p += (uint64_t)gridDim.x * kIdxBlock) {
+    const uint64_t g = order[p];
+    bool head = p == 0;
+    if (!head) {
+      const uint64_t h = order[p - 1];
+      head = mrg_cmp(mrg_key(in, h, mrg_stream(in, h)), mrg_key(in, g, mrg_stream(in, g))) != 0;
+    }
+    MrgCount c{0, 0, 0};
+    if (head) {
+      mine++;
+      const MrgGroup r = mrg_walk(in, order, p, nullptr, 0, 0);
+      if (r.emit) c = MrgCount{1, (uint32_t)r.recs, r.blob};  // recs <= the input's, < 2^32
+    }
+    cnt[p] = c;
+  }
+  if (mine) atomicAdd(heads, mine);
+}
+
+// Exclusive prefix sums of the three counts by one workgroup, as index_scan_kernel does two:
+// base[3 p], base[3 p + 1], base[3 p + 2] = entries, records, blob bytes before position p;
+// base[3 n ...] the totals.
+__global__ __launch_bounds__(kIdxScanBlock) void merge_scan_kernel(
+    const MrgCount* __restrict__ cnt, uint64_t n, uint64_t* __restrict__ base) {
+  __shared__ uint64_t a[kIdxScanBlock], b[kIdxScanBlock], c[kIdxScanBlock];
+  const uint32_t t = threadIdx.x;
+  uint64_t ca = 0, cb = 0, cc = 0;
+  for (uint64_t f0 = 0; f0 < n; f0 += kIdxScanBlock) {
+    const uint64_t f = f0 + t;
+    const MrgCount x = f < n ? cnt[f] : MrgCount{0, 0, 0};
+    a[t] = x.emit;
+    b[t] = x.recs;
+    c[t] = x.blob;
+    __syncthreads();
+    for (uint32_t d = 1; d < kIdxScanBlock; d <<= 1) {
+      const uint64_t xa = t >= d ? a[t - d] : 0, xb = t >= d ? b[t - d] : 0,
+                     xc = t >= d ? c[t - d] : 0;
+      __syncthreads();
+      a[t] += xa;
+      b[t] += xb;
+      c[t] += xc;
+      __syncthreads();
+    }
+    if (f < n) {
+      base[3 * f] = ca + a[t] - x.emit;
+      base[3 * f + 1] = cb + b[t] - x.recs;
+      base[3 * f + 2] = cc + c[t] - x.blob;
+    }
+    ca += a[kIdxScanBlock - 1];
+    cb += b[kIdxScanBlock - 1];
+    cc += c[kIdxScanBlock - 1];
+    __syncthreads();
+  }
+  if (t == 0) {
+    base[3 * n] = ca;
+    base[3 * n + 1] = cb;
+    base[3 * n + 2] = cc;
+  }
+}
+
+__global__ __launch_bounds__(kIdxBlock) void merge_fill_kernel(
+    MrgIn in, const uint32_t* __restrict__ order, const MrgCount* __restrict__ cnt,
+    const uint64_t* __restrict__ base, pfscdc_index_entry* __restrict__ entries,
+    char* __restrict__ blob, MrgCopy* __restrict__ copy) {
+  for (uint64_t p = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; p < in.n;
+       p += (uint64_t)gridDim.x * kIdxBlock) {
+    if (!cnt[p].emit) continue;
+    const uint64_t oi = base[3 * p], first = base[3 * p + 1], at0 = base[3 * p + 2];
+    const uint64_t cap = base[3 * p + 4] - first, room = base[3 * p + 5] - at0;
+    if (base[3 * p + 3] - oi != 1) continue;
+    const MrgGroup r = mrg_walk(in, order, p, copy, first, cap);
+    if (!r.emit || r.recs != cap || r.blob != room) continue;  // (never: the count pass's walk)
+    const uint64_t g0 = order[p];
+    const pfscdc_index_entry e0 = in.entries[g0];
+    const char* src = in.blob + in.blob_base[mrg_stream(in, g0)];
+    pfscdc_index_entry o = e0;
+    uint64_t at = at0;
+    o.path_off = at;
+    for (uint32_t i = 0; i < e0.path_len; i++) blob[at + i] = src[e0.path_off + i];
+    at += e0.path_len;
+    blob[at++] = 0;
+    o.tag_off = at;
+    for (uint32_t i = 0; i < e0.tag_len; i++) blob[at + i] = src[e0.tag_off + i];
+    at += e0.tag_len;
+    blob[at++] = 0;
+    o.last_path_off = at;
+    for (uint32_t i = 0; i < e0.last_path_len; i++) blob[at + i] = src[e0.last_path_off + i];
+    at += e0.last_path_len;
+    blob[at] = 0;
+    o.first = (uint32_t)first;
+    if (r.merged) {  // mergeIdx: the group's first entry with the merged File.DataRefs
+      o.flags = (e0.flags & ~(PFSCDC_IDX_HAS_CHUNK_REF | PFSCDC_IDX_HAS_RANGE)) | PFSCDC_IDX_HAS_FILE;
+      o.count = (uint32_t)r.recs;
+      o.size_bytes = r.size;
+    }
+    entries[oi] = o;
+  }
+}
+
+__global__ __launch_bounds__(kIdxBlock) void merge_copy_kernel(
+    const uint4* __restrict__ src, const MrgCopy* __restrict__ copy, uint64_t n,
+    uint4* __restrict__ dst) {
+  for (uint64_t w = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; w < n * 8;
+       w += (uint64_t)gridDim.x * kIdxBlock) {
+    const MrgCopy c = copy[w >> 3];
+    const uint32_t l = (uint32_t)(w & 7);  // 8 lanes x 16 B = one pfscdc_full_dataref
+    for (uint64_t r = 0; r < c.recs; r++) dst[((uint64_t)c.dst + r) * 8 + l] = src[((uint64_t)c.src + r) * 8 + l];
+  }
+}
+
+static unsigned merge_grid(uint64_t items, int num_cus) {
+  const uint64_t need = (items + kIdxBlock - 1) / kIdxBlock, full = (uint64_t)num_cus * 8;
+  return capped_grid(need < full ? need : full, Knob::ChachaGrid);
+}
+
+hipError_t launch_merge_rank(const MrgIn& in, uint32_t* order, uint32_t* bad, int num_cus,
+                             hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  merge_rank_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(in, order, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_merge_group(const MrgIn& in, const uint32_t* order, MrgCount* cnt,
+                              unsigned long long* heads, int num_cus, hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  merge_group_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(in, order, cnt, heads);
+  return hipGetLastError();
+}
+
+hipError_t launch_merge_scan(const MrgCount* cnt, uint64_t n, uint64_t* base, hipStream_t st) {
+  merge_scan_kernel<<<1, kIdxScanBlock, 0, st>>>(cnt, n, base);
+  return hipGetLastError();
+}
+
+hipError_t launch_merge_fill(const MrgIn& in, const uint32_t* order, const MrgCount* cnt,
+                             const uint64_t* base, pfscdc_index_entry* entries, char* blob,
+                             MrgCopy* copy, int num_cus, hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  merge_fill_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(in, order, cnt, base, entries,
+                                                                    blob, copy);
+  return hipGetLastError();
+}
+
+hipError_t launch_merge_copy(const MrgIn& in, const MrgCopy* copy, pfscdc_full_dataref* drs,
+                             int num_cus, hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  merge_copy_kernel<<<merge_grid(in.n * 8, num_cus), kIdxBlock, 0, st>>>(
+      (const uint4*)in.drs, copy, in.n, (uint4*)drs);
+  return hipGetLastError();
+}
+
 }  // namespace pfscdc

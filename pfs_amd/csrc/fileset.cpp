@@ -489,6 +489,23 @@ struct FilesetWriter {  // fileset/writer.go:21-182
     return deletive.write_index(x, 0);
   }
 
+  // Copy(file, tag) (writer.go:105-125): a fresh Index{Path, File{Tag}} through checkPath and
+  // Annotate, then every DataRef through the chunk writer's Copy
+  int copy(const std::string& path, const std::string& tag, const pfscdc_full_dataref* drs,
+           uint32_t n) {
+    IndexT* x = make(path, tag);
+    int rc = check_path(idx, x);
+    if (rc) return rc;
+    idx = x;
+    info.files.emplace_back(path, tag);
+    rc = pfscdc_writer_annotate(cw, (uint64_t)(uintptr_t)x);
+    for (uint32_t i = 0; i < n && !rc; i++) {
+      info.size_bytes = (int64_t)((uint64_t)info.size_bytes + (uint64_t)drs[i].data.size_bytes);
+      rc = pfscdc_writer_copy(cw, &drs[i]);
+    }
+    return rc;
+  }
+
   static int callback(void* user, const pfscdc_chunk_ref* chunk, const pfscdc_annotation_out* a,
                       uint32_t n) {
     FilesetWriter* w = (FilesetWriter*)user;
@@ -1269,6 +1286,197 @@ int pfscdc_uw_fileset(const pfscdc_uwriter* w, uint32_t i, pfscdc_fileset_info* 
 
 int pfscdc_uw_destroy(pfscdc_uwriter* w) {
   if (w) w->join();
+  delete w;
+  return PFSCDC_OK;
+}
+
+}  // extern "C"
+
+// fileset.Writer with a handle of its own (Storage.newWriter): Delete and Copy in path order,
+// for Compact and Concat.  Errors are sticky.
+struct pfscdc_fswriter {
+  Streams st;
+  pfscdc_store* store = nullptr;
+  std::unique_ptr<FilesetWriter> fw;
+  pfscdc_ctx* read_ctx = nullptr;  // index reads and merges: not the ctx the chunk writer is on
+  bool closed = false;
+  int err = 0;
+  std::string errmsg;
+
+  ~pfscdc_fswriter() {
+    fw.reset();
+    ctx_cache().give(read_ctx);
+  }
+  pfscdc_ctx* reader() {
+    if (!read_ctx) {
+      pfscdc_params p;
+      pfscdc_default_params(&p);
+      read_ctx = ctx_cache().take(p, pfscdc::ctx_device(st.data_ctx), 0);
+    }
+    return read_ctx;
+  }
+  int fail(int rc, const std::string& what) {
+    if (!err) {
+      err = rc;
+      errmsg = what + ": error " + std::to_string(rc);
+    }
+    return err;
+  }
+};
+
+namespace {
+
+// A run of Copies is prefetched together (the chunks its DataRefs will be re-rolled from are
+// verified side by side); the run ends once those chunks hold this many bytes, which bounds
+// the plaintext the chunk writer keeps: it is dropped after the run.
+constexpr uint64_t kCopyRunBytes = 256ull << 20;
+
+int fsw_copy_list(pfscdc_fswriter* w, const pfscdc_index_list* l) {
+  pfscdc_writer* cw = w->fw->cw;
+  const uint32_t n = pfscdc_index_list_count(l);
+  const pfscdc_index_entry* e = pfscdc_index_list_entries(l);
+  const char* blob = pfscdc_index_list_blob(l, nullptr);
+  uint32_t ndr = 0;
+  const pfscdc_full_dataref* drs = pfscdc_index_list_datarefs(l, &ndr);
+  for (uint32_t i = 0; i < n;) {
+    uint32_t j = i;
+    uint64_t held = 0;  // bytes of the distinct chunks this run re-rolls (what prefetch decrypts)
+    std::set<std::string> ids;
+    for (; j < n && (j == i || held < kCopyRunBytes); j++)
+      for (uint32_t k = e[j].first; k < e[j].first + e[j].count; k++)
+        if ((drs[k].edge || drs[k].data.offset_bytes != 0) &&
+            ids.emplace((const char*)drs[k].ref.id, 32).second)
+          held += (uint64_t)drs[k].ref_size;
+    const uint32_t first = e[i].first, last = e[j - 1].first + e[j - 1].count;
+    int rc = held ? pfscdc_writer_prefetch(cw, drs + first, last - first) : PFSCDC_OK;
+    if (rc) return w->fail(rc, "Copy (prefetch)");
+    for (; i < j; i++) {
+      rc = w->fw->copy(blob + e[i].path_off, blob + e[i].tag_off, drs + e[i].first, e[i].count);
+      if (rc) return w->fail(rc, std::string("Copy ") + (blob + e[i].path_off));
+    }
+    pfscdc::writer_drop_prefetched(cw);
+  }
+  return PFSCDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfscdc_fsw_create(pfscdc_ctx* data_ctx, const pfscdc_params* index_params, pfscdc_store* store,
+                      pfscdc_uw_cb cb, void* user, pfscdc_fswriter** out) {
+  if (!data_ctx || !store || !out) return PFSCDC_EINVAL;
+  if (!(pfscdc::ctx_options(data_ctx) & PFSCDC_OPT_REF_IDS)) return PFSCDC_EINVAL;
+  auto w = std::make_unique<pfscdc_fswriter>();
+  w->store = store;
+  w->st.cb = cb;
+  w->st.user = user;
+  w->st.store = &w->store;
+  w->st.index_params = index_params_or_default(index_params);
+  w->st.data_ctx = data_ctx;
+  w->fw = std::make_unique<FilesetWriter>(&w->st, 0);
+  if (int rc = w->fw->open()) return rc;
+  *out = w.release();
+  return PFSCDC_OK;
+}
+
+int pfscdc_fsw_delete(pfscdc_fswriter* w, const char* path, const char* tag) {
+  if (!w || !path) return PFSCDC_EINVAL;
+  if (w->err) return w->err;
+  if (w->closed) return w->fail(PFSCDC_ESTATE, "Delete after Close");
+  const int rc = w->fw->del(path, tag ? tag : "");
+  return rc ? w->fail(rc, std::string("Delete ") + path) : PFSCDC_OK;
+}
+
+int pfscdc_fsw_copy(pfscdc_fswriter* w, const char* path, const char* tag,
+                    const pfscdc_full_dataref* drs, uint32_t n) {
+  if (!w || !path || (n && !drs)) return PFSCDC_EINVAL;
+  if (w->err) return w->err;
+  if (w->closed) return w->fail(PFSCDC_ESTATE, "Copy after Close");
+  const int rc = w->fw->copy(path, tag ? tag : "", drs, n);
+  return rc ? w->fail(rc, std::string("Copy ") + path) : PFSCDC_OK;
+}
+
+int pfscdc_fsw_copy_lists(pfscdc_fswriter* w, const pfscdc_index_list* additive,
+                          const pfscdc_index_list* deletive) {
+  if (!w) return PFSCDC_EINVAL;
+  if (w->err) return w->err;
+  if (w->closed) return w->fail(PFSCDC_ESTATE, "CopyFiles after Close");
+  // CopyFiles(ctx, w, fs, true): every deletive entry as a Delete, then every file as a Copy
+  const uint32_t nd = pfscdc_index_list_count(deletive);
+  const pfscdc_index_entry* e = pfscdc_index_list_entries(deletive);
+  const char* blob = pfscdc_index_list_blob(deletive, nullptr);
+  for (uint32_t i = 0; i < nd; i++) {
+    const int rc = w->fw->del(blob + e[i].path_off, blob + e[i].tag_off);
+    if (rc) return w->fail(rc, std::string("Delete ") + (blob + e[i].path_off));
+  }
+  return fsw_copy_list(w, additive);
+}
+
+int pfscdc_fsw_copy_filesets(pfscdc_fswriter* w, const pfscdc_fileset_info* filesets, uint32_t n,
+                             const pfscdc_index_filter* filter) {
+  if (!w || (n && !filesets)) return PFSCDC_EINVAL;
+  if (w->err) return w->err;
+  if (w->closed) return w->fail(PFSCDC_ESTATE, "CopyFiles after Close");
+  if (n == 0) return PFSCDC_OK;  // Storage.Open: emptyFileSet
+  // Storage.Open(ids, opts...): both roots of every fileset through the index reader
+  struct Free {
+    void operator()(pfscdc_index_list* l) const { pfscdc_index_list_free(l); }
+  };
+  using Owned = std::unique_ptr<pfscdc_index_list, Free>;
+  pfscdc_ctx* ctx = w->reader();
+  if (!ctx) return w->fail(PFSCDC_EHIP, "Open: no context for the index reads");
+  std::vector<Owned> lists(2 * (size_t)n);  // fileset k: its deletive list, then its additive
+  std::vector<const pfscdc_index_list*> all(2 * (size_t)n), dele(n);
+  for (uint32_t k = 0; k < n; k++)
+    for (int which = 0; which < 2; which++) {
+      const pfscdc_fileset_info& f = filesets[k];
+      pfscdc_index_list* l = nullptr;
+      const int rc = pfscdc_index_read(ctx, w->store, which ? f.additive_root : f.deletive_root,
+                                       which ? f.additive_root_len : f.deletive_root_len, filter, &l);
+      if (rc) return w->fail(rc, std::string("Open: ") + pfscdc_last_error(ctx));
+      lists[2 * k + which].reset(l);
+      all[2 * k + which] = l;
+      if (!which) dele[k] = l;
+    }
+  if (n == 1)  // one fileset is read with no merge
+    return pfscdc_fsw_copy_lists(w, all[1], all[0]);
+  pfscdc_index_list *files = nullptr, *deletes = nullptr;
+  int rc = pfscdc_index_merge_ctx(ctx, PFSCDC_MERGE_DELETIVE, dele.data(), n, &deletes);
+  Owned own_d(deletes);
+  if (!rc) rc = pfscdc_index_merge_ctx(ctx, PFSCDC_MERGE_FILES, all.data(), n, &files);
+  Owned own_f(files);
+  if (rc) return w->fail(rc, std::string("merge: ") + pfscdc_last_error(ctx));
+  return pfscdc_fsw_copy_lists(w, files, deletes);
+}
+
+int pfscdc_fsw_close(pfscdc_fswriter* w) {
+  if (!w) return PFSCDC_EINVAL;
+  if (w->err) return w->err;
+  if (w->closed) return PFSCDC_OK;
+  w->closed = true;
+  const int rc = w->fw->close();
+  return rc ? w->fail(rc, "Close") : PFSCDC_OK;
+}
+
+int pfscdc_fsw_fileset(const pfscdc_fswriter* w, pfscdc_fileset_info* out) {
+  if (!w || !out || !w->closed || w->err) return PFSCDC_EINVAL;
+  const FilesetInfo& f = w->fw->info;
+  out->size_bytes = f.size_bytes;
+  out->additive_root = f.has_additive ? (const uint8_t*)f.additive.data() : nullptr;
+  out->additive_root_len = f.has_additive ? f.additive.size() : 0;
+  out->deletive_root = f.has_deletive ? (const uint8_t*)f.deletive.data() : nullptr;
+  out->deletive_root_len = f.has_deletive ? f.deletive.size() : 0;
+  out->num_files = (uint32_t)f.files.size();
+  out->num_deletes = (uint32_t)f.deletes.size();
+  return PFSCDC_OK;
+}
+
+const char* pfscdc_fsw_last_error(const pfscdc_fswriter* w) {
+  return w ? w->errmsg.c_str() : "null fileset writer";
+}
+
+int pfscdc_fsw_destroy(pfscdc_fswriter* w) {
   delete w;
   return PFSCDC_OK;
 }

@@ -262,9 +262,176 @@ int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const
   return rc ? ctx_fail(ctx, rc, "more than 2^32 index records") : PFSCDC_OK;
 }
 
+// MergeReader on the device (cdc_kernels.hip §9) over ns streams.  *ran = false: the call
+// belongs to the host arm (a stream out of order, or more than 2^32 - 1 entries or records).
+// Every output array is allocated kMrgGuard bytes longer and the guard, preset to 0xA5, is read
+// back with the list: a kernel that wrote past what the prefix sums counted fails the call.
+constexpr uint64_t kMrgGuard = 64;
+
+int merge_device(pfscdc_ctx* ctx, int mode, const List* const* lists, uint32_t ns, List* out,
+                 bool* ran) {
+  MergeStats& st = ctx_merge_stats(ctx);
+  *ran = false;
+  std::vector<uint64_t> tab(3 * (uint64_t)ns + 1, 0);  // stream_begin[ns + 1], blob_base, dr_base
+  uint64_t *sb = tab.data(), *bb = sb + ns + 1, *db = bb + ns;
+  uint64_t n = 0, nb = 0, nr = 0;
+  for (uint32_t s = 0; s < ns; s++) {
+    sb[s] = n;
+    bb[s] = nb;
+    db[s] = nr;
+    if (!lists[s]) continue;
+    n += lists[s]->entries.size();
+    nb += lists[s]->blob.size();
+    nr += lists[s]->drs.size();
+  }
+  sb[ns] = n;
+  st.n[1] = n;
+  if (n > 0xffffffffull || nr > 0xffffffffull) return PFSCDC_OK;
+  *ran = true;
+  if (n == 0) return PFSCDC_OK;
+  hipStream_t s = ctx_stream(ctx);
+  const int cus = ctx_num_cus(ctx);
+  IDX_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  // ---- upload: the streams' three arrays, concatenated stream-major
+  auto t0 = Clock::now();
+  DevMem d_tab, d_entries, d_blob, d_drs, d_order, d_bad, d_cnt, d_base, d_heads;
+  IDX_HIP(ctx, d_tab.alloc(sizeof(uint64_t) * tab.size()));
+  IDX_HIP(ctx, d_entries.alloc(sizeof(pfscdc_index_entry) * n));
+  IDX_HIP(ctx, d_blob.alloc(nb));
+  IDX_HIP(ctx, d_drs.alloc(sizeof(pfscdc_full_dataref) * nr));
+  IDX_HIP(ctx, d_order.alloc(sizeof(uint32_t) * n));
+  IDX_HIP(ctx, d_bad.alloc(sizeof(uint32_t)));
+  IDX_HIP(ctx, d_heads.alloc(sizeof(uint64_t)));
+  IDX_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * n));
+  IDX_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (n + 1)));
+  IDX_HIP(ctx, hipMemcpyAsync(d_tab.p, tab.data(), sizeof(uint64_t) * tab.size(), hipMemcpyHostToDevice, s));
+  for (uint32_t k = 0; k < ns; k++) {
+    const List* l = lists[k];
+    if (!l) continue;
+    if (!l->entries.empty())
+      IDX_HIP(ctx, hipMemcpyAsync(d_entries.as<pfscdc_index_entry>() + sb[k], l->entries.data(),
+                                  sizeof(pfscdc_index_entry) * l->entries.size(), hipMemcpyHostToDevice, s));
+    if (!l->blob.empty())
+      IDX_HIP(ctx, hipMemcpyAsync(d_blob.as<char>() + bb[k], l->blob.data(), l->blob.size(),
+                                  hipMemcpyHostToDevice, s));
+    if (!l->drs.empty())
+      IDX_HIP(ctx, hipMemcpyAsync(d_drs.as<pfscdc_full_dataref>() + db[k], l->drs.data(),
+                                  sizeof(pfscdc_full_dataref) * l->drs.size(), hipMemcpyHostToDevice, s));
+  }
+  IDX_HIP(ctx, hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
+  IDX_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[0] = ms_since(t0);
+  // ---- rank, then group and count, then the prefix sums
+  t0 = Clock::now();
+  const MrgIn in{d_entries.as<pfscdc_index_entry>(), d_blob.as<char>(), d_drs.as<pfscdc_full_dataref>(),
+                 d_tab.as<uint64_t>(), d_tab.as<uint64_t>() + ns + 1, d_tab.as<uint64_t>() + 2 * (uint64_t)ns + 1,
+                 n, ns, mode};
+  uint32_t bad = 0;
+  IDX_HIP(ctx, launch_merge_rank(in, d_order.as<uint32_t>(), d_bad.as<uint32_t>(), cus, s));
+  IDX_HIP(ctx, hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipStreamSynchronize(s));
+  if (bad) {  // a stream is not strictly ascending: the ranks are no permutation
+    st.ms[1] = ms_since(t0);
+    *ran = false;
+    return PFSCDC_OK;
+  }
+  uint64_t totals[3] = {0, 0, 0}, heads = 0;
+  IDX_HIP(ctx, hipMemsetAsync(d_heads.p, 0, sizeof(uint64_t), s));
+  IDX_HIP(ctx, launch_merge_group(in, d_order.as<uint32_t>(), d_cnt.as<MrgCount>(),
+                                  d_heads.as<unsigned long long>(), cus, s));
+  IDX_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), n, d_base.as<uint64_t>(), s));
+  IDX_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 3 * n, sizeof totals, hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipMemcpyAsync(&heads, d_heads.p, sizeof heads, hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[1] = ms_since(t0);
+  if (totals[0] > n || totals[1] > nr || totals[2] > nb)  // (the output is a part of the input)
+    return ctx_fail(ctx, PFSCDC_EHIP, "index merge: the counts exceed the input");
+  // ---- emit: entries, strings and the copy plan, then the DataRefs
+  t0 = Clock::now();
+  const uint64_t eb = sizeof(pfscdc_index_entry) * totals[0], rb = sizeof(pfscdc_full_dataref) * totals[1];
+  DevMem d_oe, d_ob, d_or, d_copy;
+  IDX_HIP(ctx, d_oe.alloc(eb + kMrgGuard));
+  IDX_HIP(ctx, d_ob.alloc(totals[2] + kMrgGuard));
+  IDX_HIP(ctx, d_or.alloc(rb + kMrgGuard));
+  IDX_HIP(ctx, d_copy.alloc(sizeof(MrgCopy) * n));
+  IDX_HIP(ctx, hipMemsetAsync(d_oe.as<char>() + eb, 0xA5, kMrgGuard, s));
+  IDX_HIP(ctx, hipMemsetAsync(d_ob.as<char>() + totals[2], 0xA5, kMrgGuard, s));
+  IDX_HIP(ctx, hipMemsetAsync(d_or.as<char>() + rb, 0xA5, kMrgGuard, s));
+  IDX_HIP(ctx, hipMemsetAsync(d_copy.p, 0, sizeof(MrgCopy) * n, s));
+  IDX_HIP(ctx, launch_merge_fill(in, d_order.as<uint32_t>(), d_cnt.as<MrgCount>(), d_base.as<uint64_t>(),
+                                 d_oe.as<pfscdc_index_entry>(), d_ob.as<char>(), d_copy.as<MrgCopy>(), cus, s));
+  IDX_HIP(ctx, launch_merge_copy(in, d_copy.as<MrgCopy>(), d_or.as<pfscdc_full_dataref>(), cus, s));
+  IDX_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[2] = ms_since(t0);
+  // ---- the list to the host
+  t0 = Clock::now();
+  uint8_t guard[3][kMrgGuard];
+  out->entries.resize(totals[0]);
+  out->drs.resize(totals[1]);
+  out->blob.resize(totals[2]);
+  if (eb) IDX_HIP(ctx, hipMemcpyAsync(out->entries.data(), d_oe.p, eb, hipMemcpyDeviceToHost, s));
+  if (rb) IDX_HIP(ctx, hipMemcpyAsync(out->drs.data(), d_or.p, rb, hipMemcpyDeviceToHost, s));
+  if (totals[2]) IDX_HIP(ctx, hipMemcpyAsync(out->blob.data(), d_ob.p, totals[2], hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipMemcpyAsync(guard[0], d_oe.as<char>() + eb, kMrgGuard, hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipMemcpyAsync(guard[1], d_ob.as<char>() + totals[2], kMrgGuard, hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipMemcpyAsync(guard[2], d_or.as<char>() + rb, kMrgGuard, hipMemcpyDeviceToHost, s));
+  IDX_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[3] = ms_since(t0);
+  for (auto& g : guard)
+    for (uint8_t b : g)
+      if (b != 0xA5) return ctx_fail(ctx, PFSCDC_EHIP, "index merge: a kernel wrote past its array");
+  st.n[2] = heads;
+  st.n[3] = totals[0];
+  return PFSCDC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pfscdc_index_merge_ctx(pfscdc_ctx* ctx, int mode, const pfscdc_index_list* const* lists,
+                           uint32_t nfilesets, pfscdc_index_list** out) {
+  if (!ctx || !out || (nfilesets && !lists) || nfilesets > (1u << 30) ||
+      (mode != PFSCDC_MERGE_FILES && mode != PFSCDC_MERGE_DELETIVE))
+    return PFSCDC_EINVAL;
+  *out = nullptr;
+  MergeStats& st = pfscdc::ctx_merge_stats(ctx);
+  st = MergeStats();
+  const uint32_t ns = mode == PFSCDC_MERGE_FILES ? 2 * nfilesets : nfilesets;
+  if (pfscdc::knob(pfscdc::Knob::IndexMerge) != 0) {
+    std::unique_ptr<List> l(new List());
+    bool ran = false;
+    if (int rc = merge_device(ctx, mode, lists, ns, l.get(), &ran)) return rc;
+    if (ran) {
+      st.n[0] = 1;
+      *out = l.release();
+      return PFSCDC_OK;
+    }
+  }
+  uint64_t n_in = 0;
+  for (uint32_t k = 0; k < ns; k++) n_in += lists[k] ? lists[k]->entries.size() : 0;
+  auto t0 = Clock::now();
+  const int rc = mode == PFSCDC_MERGE_FILES ? pfscdc_index_merge(lists, nfilesets, out)
+                                            : pfscdc_index_merge_deletive(lists, nfilesets, out);
+  st.ms[1] += ms_since(t0);
+  st.n[0] = 0;
+  st.n[1] = n_in;
+  st.n[3] = *out ? (*out)->entries.size() : 0;
+  if (rc) return pfscdc::ctx_fail(ctx, rc, "index merge: more than 2^32 - 1 records in the merged list");
+  return PFSCDC_OK;
+}
+
+int pfscdc_last_merge_stats(pfscdc_ctx* ctx, uint64_t out[4]) {
+  if (!ctx || !out) return PFSCDC_EINVAL;
+  std::memcpy(out, pfscdc::ctx_merge_stats(ctx).n, sizeof(uint64_t) * 4);
+  return PFSCDC_OK;
+}
+
+int pfscdc_last_merge_timings(pfscdc_ctx* ctx, float out[4]) {
+  if (!ctx || !out) return PFSCDC_EINVAL;
+  std::memcpy(out, pfscdc::ctx_merge_stats(ctx).ms, sizeof(float) * 4);
+  return PFSCDC_OK;
+}
 
 int pfscdc_index_read(pfscdc_ctx* ctx, const pfscdc_store* store, const void* root,
                       uint64_t root_len, const pfscdc_index_filter* filter,

@@ -169,11 +169,13 @@ struct pfscdc_ctx {
   const uint8_t* dev_data = nullptr;  // data pointer of the last scan
   pfscdc_ctx* hash_after = nullptr;   // pfscdc_order_hash_after
   IndexStats index_stats;             // the last pfscdc_index_read
+  MergeStats merge_stats;             // the last pfscdc_index_merge_ctx
 };
 
 namespace pfscdc {
 const pfscdc_params& ctx_params(const pfscdc_ctx* ctx) { return ctx->params; }
 IndexStats& ctx_index_stats(pfscdc_ctx* ctx) { return ctx->index_stats; }
+MergeStats& ctx_merge_stats(pfscdc_ctx* ctx) { return ctx->merge_stats; }
 int ctx_num_cus(const pfscdc_ctx* ctx) { return ctx->num_cus; }
 }  // namespace pfscdc
 

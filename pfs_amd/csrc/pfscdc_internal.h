@@ -47,7 +47,7 @@ enum class Knob : int {
   HashBinBytes, HashWaves, HashFair, HashFairEvery,
   RefIdSplit, CommitTwoSets, CommitLongPct,
   UwWorkers, UwInflight, UwMirror, UwIndexGrouped, UwArenaPoolBytes, CtxCache, CopyThreads,
-  IndexDecode, Trace,
+  IndexDecode, IndexMerge, Trace,
   kCount
 };
 int64_t knob(Knob k);
@@ -95,6 +95,9 @@ int writers_close_group(pfscdc_writer* const* ws, size_t n, double* stage_ms = n
 // (nullable): the same bytes already on the writer's device
 int writer_write_span(pfscdc_writer* w, const uint8_t* p, uint64_t n,
                       const uint8_t* dev = nullptr);
+// the chunks pfscdc_writer_prefetch decrypted ahead and no Copy has to see again: dropped (a
+// fileset writer prefetches run by run, so the plaintext held is one run's)
+void writer_drop_prefetched(pfscdc_writer* w);
 uint32_t ctx_options(const pfscdc_ctx* ctx);
 // the last completed scan: still readable (no create_refs / get_chunks since), its files
 bool ctx_scan_valid(const pfscdc_ctx* ctx);
@@ -306,6 +309,50 @@ struct IndexStats {
 };
 IndexStats& ctx_index_stats(pfscdc_ctx* ctx);
 int ctx_num_cus(const pfscdc_ctx* ctx);
+// ---- MergeReader on the device (index.cpp; kernels in cdc_kernels.hip) ----
+// The streams of one merge, concatenated stream-major on the device: stream s holds entries
+// [stream_begin[s], stream_begin[s + 1]), whose string offsets count from blob + blob_base[s]
+// and whose DataRef indexes from drs + dr_base[s].
+struct MrgIn {
+  const pfscdc_index_entry* entries;
+  const char* blob;
+  const pfscdc_full_dataref* drs;
+  const uint64_t *stream_begin, *blob_base, *dr_base;  // ns + 1, ns, ns
+  uint64_t n;   // entries in all (< 2^32)
+  uint32_t ns;  // streams
+  int mode;     // PFSCDC_MERGE_*
+};
+struct MrgCount {  // per merged position: what the group that begins there emits
+  uint32_t emit, recs;
+  uint64_t blob;
+};
+struct MrgCopy {  // per source entry: its recs DataRefs drs[src, ...) go to out[dst, ...)
+  uint32_t dst, recs, src, reserved;
+};
+// order[rank of entry e in the merged order] = e; *bad |= 1 if a stream is not strictly
+// ascending in (path, tag) (order is then not a permutation and must not be used)
+hipError_t launch_merge_rank(const MrgIn& in, uint32_t* order, uint32_t* bad, int num_cus,
+                             hipStream_t st);
+// cnt[p] for every merged position p ({0, 0, 0} where no emitting group begins); *heads (zeroed
+// before) += the groups
+hipError_t launch_merge_group(const MrgIn& in, const uint32_t* order, MrgCount* cnt,
+                              unsigned long long* heads, int num_cus, hipStream_t st);
+// exclusive prefix sums of cnt[0, n) into base[0, n]: {entries, records, blob bytes} each
+hipError_t launch_merge_scan(const MrgCount* cnt, uint64_t n, uint64_t* base, hipStream_t st);
+// entries[base[3p]], its strings at blob + base[3p + 2], and copy[] (zeroed before) for the
+// source entries whose DataRefs go to drs[base[3p + 1], ...)
+hipError_t launch_merge_fill(const MrgIn& in, const uint32_t* order, const MrgCount* cnt,
+                             const uint64_t* base, pfscdc_index_entry* entries, char* blob,
+                             MrgCopy* copy, int num_cus, hipStream_t st);
+// the DataRefs copy[] names, 16 bytes per lane
+hipError_t launch_merge_copy(const MrgIn& in, const MrgCopy* copy, pfscdc_full_dataref* drs,
+                             int num_cus, hipStream_t st);
+// what pfscdc_last_merge_stats / pfscdc_last_merge_timings report
+struct MergeStats {
+  uint64_t n[4] = {};
+  float ms[4] = {};
+};
+MergeStats& ctx_merge_stats(pfscdc_ctx* ctx);
 
 hipError_t launch_synth(uint8_t* out, const uint64_t* offs, uint32_t nfiles, const uint32_t* ids,
                         const uint64_t* starts, uint64_t seed, uint32_t mode, hipStream_t st);

@@ -856,6 +856,10 @@ int writer_write_span(pfscdc_writer* w, const uint8_t* p, uint64_t n, const uint
   return PFSCDC_OK;
 }
 
+void writer_drop_prefetched(pfscdc_writer* w) {
+  if (w) w->plain.clear();
+}
+
 }  // namespace pfscdc
 
 extern "C" {

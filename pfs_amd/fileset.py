@@ -304,19 +304,60 @@ def index_filter(lst: IndexList, lower=None, upper=None, prefix=None, tag=None) 
     return IndexList(out)
 
 
-def index_merge(pairs) -> IndexList:
+def index_merge(pairs, chunker=None, deletive: bool = False) -> IndexList:
     """MergeReader.iterate over (deletive list, additive list) pairs in fileset order
-    (pfscdc_index_merge); None stands for an empty list."""
+    (pfscdc_index_merge); None stands for an empty list.  ``deletive``: iterateDeletive over
+    the pairs' deletive lists (pfscdc_index_merge_deletive).  With a ``chunker`` the merge goes
+    through pfscdc_index_merge_ctx on its context: on the device or on the host by the
+    PFSCDC_INDEX_MERGE knob, with the same list either way."""
     pairs = list(pairs)
-    arr = (C.c_void_p * max(1, 2 * len(pairs)))()
-    for i, (d, a) in enumerate(pairs):
-        arr[2 * i] = d._p if d is not None else None
-        arr[2 * i + 1] = a._p if a is not None else None
+    lists = [d for d, _ in pairs] if deletive else [x for d, a in pairs for x in (d, a)]
+    arr = (C.c_void_p * max(1, len(lists)))()
+    for i, l in enumerate(lists):
+        arr[i] = l._p if l is not None else None
     out = C.c_void_p()
-    rc = _lib.load().pfscdc_index_merge(arr, len(pairs), C.byref(out))
+    if chunker is not None:
+        rc = chunker.lib.pfscdc_index_merge_ctx(
+            chunker.ctx, _lib.MERGE_DELETIVE if deletive else _lib.MERGE_FILES, arr, len(pairs),
+            C.byref(out))
+        if rc:
+            msg = chunker.lib.pfscdc_last_error(chunker.ctx)
+            raise _lib.PfsCdcError(rc, f"index merge: {msg.decode() if msg else ''}")
+        return IndexList(out)
+    lib = _lib.load()
+    fn = lib.pfscdc_index_merge_deletive if deletive else lib.pfscdc_index_merge
+    rc = fn(arr, len(pairs), C.byref(out))
     if rc:
-        raise _lib.PfsCdcError(rc, "pfscdc_index_merge")
+        raise _lib.PfsCdcError(rc, fn.__name__)
     return IndexList(out)
+
+
+def last_merge_stats(chunker) -> dict:
+    """Counts and stage times (ms) of the last index_merge on ``chunker``'s context."""
+    n, ms = (C.c_uint64 * 4)(), (C.c_float * 4)()
+    chunker.lib.pfscdc_last_merge_stats(chunker.ctx, n)
+    chunker.lib.pfscdc_last_merge_timings(chunker.ctx, ms)
+    out = dict(zip(["device", "entries_in", "groups", "entries_out"], [int(x) for x in n]))
+    out.update(zip(["upload_ms", "rank_group_ms", "emit_ms", "d2h_ms"],
+                   [round(float(x), 4) for x in ms]))
+    return out
+
+
+def shard(files: IndexList, threshold: int = DEFAULT_MEMORY_THRESHOLD) -> list:
+    """shard (shard.go:27-49) over a merged list: the (lower, upper) path ranges, "" an open
+    end (pfscdc_shard)."""
+    out = []
+
+    def cb(_user, lower, upper):
+        out.append((lower.decode("utf-8", "surrogateescape"),
+                    upper.decode("utf-8", "surrogateescape")))
+        return 0
+
+    rc = _lib.load().pfscdc_shard(files._p if files is not None else None, threshold,
+                                  _lib.SHARD_CB(cb), None)
+    if rc:
+        raise _lib.PfsCdcError(rc, "pfscdc_shard")
+    return out
 
 
 def index_read(chunker, store, root: Optional[bytes], lower=None, upper=None, prefix=None,
@@ -458,9 +499,61 @@ class Storage:
             pairs = [(index_read(c, self.store, d, lower, upper, prefix, tag),
                       index_read(c, self.store, a, lower, upper, prefix, tag))
                      for a, d in roots]
+            merged = index_merge(pairs, chunker=c)
         finally:
             c.close()
-        return FileSet(self, index_merge(pairs))
+        return FileSet(self, merged)
+
+    def shard(self, filesets, threshold: int = 10 ** 9) -> list:
+        """``Storage.Shard`` (shard.go:12-18): the (lower, upper) path ranges, "" an open end,
+        that split the merged view of ``filesets`` into runs of ``threshold`` content bytes."""
+        return shard(self.open(filesets)._list, threshold)
+
+    @staticmethod
+    def _infos(filesets):
+        """pfscdc_fileset_info array of ``Primitive``s, (additive, deletive) pairs or bare
+        additive roots; the second value keeps the roots' buffers alive."""
+        arr = (_lib.FilesetInfo * max(1, len(filesets)))()
+        keep = []
+        for i, fs in enumerate(filesets):
+            if isinstance(fs, (bytes, bytearray)) or fs is None:
+                a, d = fs, None
+            elif isinstance(fs, tuple):
+                a, d = fs
+            else:
+                a, d = fs.additive, fs.deletive
+            for name, root in (("additive", a), ("deletive", d)):
+                if root:
+                    buf = C.create_string_buffer(bytes(root), len(root))
+                    keep.append(buf)
+                    setattr(arr[i], name + "_root", C.cast(buf, C.c_void_p))
+                    setattr(arr[i], name + "_root_len", len(root))
+        return arr, keep
+
+    def new_writer(self) -> "FilesetWriter":
+        """``Storage.newWriter``: a ``fileset.Writer`` with Delete and Copy."""
+        return FilesetWriter(self)
+
+    def compact(self, filesets, lower=None, upper=None, prefix=None) -> Primitive:
+        """``Storage.Compact`` (compaction.go:43-57): ``filesets`` opened with the path range,
+        merged, and copied into one new fileset (``CopyFiles(ctx, w, fs, true)``)."""
+        w = self.new_writer()
+        try:
+            w.copy_filesets(filesets, lower, upper, prefix)
+            return w.close()
+        finally:
+            w.release()
+
+    def concat(self, filesets) -> Primitive:
+        """``Storage.Concat`` (storage.go:226-238): each fileset copied in turn into one new
+        fileset; their path ranges must not overlap and must come in order."""
+        w = self.new_writer()
+        try:
+            for fs in filesets:
+                w.copy_filesets([fs])
+            return w.close()
+        finally:
+            w.release()
 
     def _take_chunker(self):
         # a context (stream, events, device staging) per GPU, reused writer after writer, as
@@ -491,6 +584,119 @@ class Storage:
             raise _lib.PfsCdcError(rc, "pfscdc_uw_trim_cache")
         return {"data_contexts": n_idle, "arena_bytes": int(freed.value),
                 "cached_contexts": int(ctxs.value)}
+
+
+class FilesetWriter:
+    """``fileset.Writer`` over pfscdc_fsw_*: ``delete`` and ``copy`` in path order, ``close``
+    returns the ``Primitive``.  ``events``: every formed chunk as ("chunk", index, level, size,
+    edge, Ref.Id, copied) -- copied: a data chunk passed through by reference -- and every
+    level-0 index entry as ("index", which, frame).  Errors are sticky."""
+
+    def __init__(self, storage: Storage):
+        self.lib = _lib.load()
+        if storage.store is None:
+            raise ValueError("the storage has no chunk store to copy from")
+        self._storage = storage
+        # one fileset on one GPU: a device group's Storage writes it on its first device
+        self._own = storage.devices is not None
+        self._chunker = Chunker(storage.params, storage.devices[0], ref_ids=True) if self._own \
+            else storage._take_chunker()
+        self.events: list = []
+        self._exc: Optional[BaseException] = None
+        ref = weakref.ref(self)
+
+        def on_event(user, ev_p, _ref=ref):
+            o = _ref()
+            return o._on_event(user, ev_p) if o is not None else 1
+
+        self._cfun = _lib.UW_CB(on_event)
+        ip = storage.index_params.to_c() if storage.index_params else None
+        w = C.c_void_p()
+        rc = self.lib.pfscdc_fsw_create(self._chunker.ctx, C.byref(ip) if ip is not None else None,
+                                        storage.store._s, self._cfun, None, C.byref(w))
+        if rc:
+            self.release()
+            raise _lib.PfsCdcError(rc, "pfscdc_fsw_create")
+        self._w = w
+
+    def _on_event(self, _user, ev_p) -> int:
+        try:
+            ev = ev_p.contents
+            if ev.kind == _lib.EV_CHUNK:
+                ch = ev.chunk
+                self.events.append(("chunk", ev.index, ev.level if ev.index >= 0 else 0,
+                                    ch.size_bytes, bool(ch.edge), bytes(ch.ref.id),
+                                    bool(ch.copied)))
+            else:
+                self.events.append(("index", ev.index, C.string_at(ev.bytes, ev.len)))
+            return 0
+        except BaseException as e:
+            self._exc = e
+            return 1
+
+    def _check(self, rc: int, what: str) -> None:
+        if self._exc is not None:
+            exc, self._exc = self._exc, None
+            raise exc
+        if rc:
+            msg = self.lib.pfscdc_fsw_last_error(self._w) if getattr(self, "_w", None) else None
+            raise _lib.PfsCdcError(rc, f"{what}: {msg.decode() if msg else ''}")
+
+    def delete(self, p: str, tag: str = "") -> None:
+        self._check(self.lib.pfscdc_fsw_delete(self._w, p.encode(), tag.encode()), "Delete")
+
+    def copy(self, p: str, tag: str, data_refs) -> None:
+        """``Writer.Copy``: the file ``p`` under ``tag`` made of ``data_refs`` (DataRefs with
+        their chunks' Refs, in the store)."""
+        from .chunk import _full
+
+        arr = (_lib.FullDataRef * max(1, len(data_refs)))()
+        for i, d in enumerate(data_refs):
+            arr[i] = _full(d)
+        self._check(self.lib.pfscdc_fsw_copy(self._w, p.encode(), tag.encode(), arr,
+                                             len(data_refs)), "Copy")
+
+    def copy_lists(self, additive: Optional[IndexList], deletive: Optional[IndexList]) -> None:
+        """``CopyFiles(ctx, w, fs, true)`` over an opened fileset's two lists."""
+        self._check(self.lib.pfscdc_fsw_copy_lists(
+            self._w, additive._p if additive is not None else None,
+            deletive._p if deletive is not None else None), "CopyFiles")
+
+    def copy_filesets(self, filesets, lower=None, upper=None, prefix=None) -> None:
+        """``Open(ids, opts...)`` and ``CopyFiles``: the filesets read with the path range,
+        merged and copied."""
+        filesets = list(filesets)
+        arr, keep = Storage._infos(filesets)
+        f = _filter(lower, upper, prefix, None)
+        self._check(self.lib.pfscdc_fsw_copy_filesets(
+            self._w, arr, len(filesets), C.byref(f) if f is not None else None), "CopyFiles")
+        del keep
+
+    def close(self) -> Primitive:
+        self._check(self.lib.pfscdc_fsw_close(self._w), "Close")
+        info = _lib.FilesetInfo()
+        self._check(self.lib.pfscdc_fsw_fileset(self._w, C.byref(info)), "fileset")
+        a = C.string_at(info.additive_root, info.additive_root_len) if info.additive_root else None
+        d = C.string_at(info.deletive_root, info.deletive_root_len) if info.deletive_root else None
+        return Primitive(a, d, info.size_bytes, info.num_files, info.num_deletes)
+
+    def release(self) -> None:
+        """Destroy the writer and hand its data context back to the Storage."""
+        if getattr(self, "_w", None):
+            self.lib.pfscdc_fsw_destroy(self._w)
+            self._w = None
+        if getattr(self, "_chunker", None):
+            if self._own:
+                self._chunker.close()
+            else:
+                self._storage._give_chunker(self._chunker)
+            self._chunker = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 class UnorderedWriter:

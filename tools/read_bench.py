@@ -30,8 +30,22 @@ Every list is compared, array for array, with pfscdc_index_decode_host over the 
 level-0 index events, and its first and last 500 entries with the events decoded by the protobuf
 runtime.  Writes profiles/r9/index_read/index_read.json.
 
-usage: python tools/read_bench.py [--tar | --index] [--chunks N] [--chunk-bytes B] [--reps R]
-                                  [--warmup W] [--out PATH]"""
+--merge: MergeReader over index lists (pfscdc_index_merge_ctx), the device arm
+(PFSCDC_INDEX_MERGE=1) and the host arm (0) alternating call by call, in both modes (iterate,
+iterateDeletive).  Two shapes, each file Put without append (a deletive and an additive entry
+with one DataRef per file): two filesets of 524,288 files, and ten filesets of 104,858 files
+of which 10,486 are in every fileset.  The lists are assembled from fixed-layout frames and
+decoded by pfscdc_index_decode_host.  Per arm: median, min and max of the call's wall time and
+of the device arm's stages; every output is compared array for array between the arms.  Writes
+profiles/r10/compact/merge.json.
+
+--compact: one compaction of a commit of two filesets (--files files of 256 B: the even files,
+then the odd files again with every 16th file deleted), split into index reads, merges, copies
+(cheap-copied against re-rolled bytes) and close.  Writes profiles/r10/compact/compact.json.
+
+usage: python tools/read_bench.py [--tar | --index | --merge | --compact] [--chunks N]
+                                  [--chunk-bytes B] [--files N] [--reps R] [--warmup W]
+                                  [--out PATH]"""
 import argparse
 import json
 import os
@@ -229,9 +243,192 @@ def index_rows(args):
     return rows
 
 
+def synthetic_lists(ids, seed):
+    """The deletive and additive index lists of one fileset whose files are /bench/dDDD/fNNNNNNN
+    for N in ids (ascending), each Put without append (so every file has a deletive entry too)
+    and one DataRef of 256 bytes: fixed-layout frames assembled with numpy, decoded by
+    pfscdc_index_decode_host.  Returns (deletive, additive, one additive frame)."""
+    from pfs_amd import fileset as PF
+    ids = np.asarray(ids, dtype=np.int64)
+    n = len(ids)
+    rng = np.random.default_rng(seed)
+
+    def path_cols(m, at):
+        m[:, at:at + 8] = np.frombuffer(b"/bench/d", dtype=np.uint8)
+        d = ids >> 12
+        for k in range(3):
+            m[:, at + 8 + k] = 48 + (d // 10 ** (2 - k)) % 10
+        m[:, at + 11:at + 13] = np.frombuffer(b"/f", dtype=np.uint8)
+        for k in range(7):
+            m[:, at + 13 + k] = 48 + (ids // 10 ** (6 - k)) % 10
+
+    a = np.zeros((n, 159), dtype=np.uint8)
+    a[:, 0] = 151  # int64 LE frame length
+    a[:, 8:10] = (0x0A, 20)  # path
+    path_cols(a, 10)
+    a[:, 30:34] = (0x1A, 127, 0x0A, 7)  # file { tag
+    a[:, 34:41] = np.frombuffer(b"default", dtype=np.uint8)
+    a[:, 41:47] = (0x12, 116, 0x0A, 73, 0x0A, 32)  # data_refs { ref { id
+    a[:, 47:79] = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    a[:, 79:84] = (0x10, 0x80, 0xA4, 0xE8, 0x03)  # Ref.size_bytes 8,000,000
+    a[:, 84:86] = (0x22, 32)  # dek
+    a[:, 86:118] = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    a[:, 118:120] = (0x12, 32)  # hash
+    a[:, 120:152] = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    off = 16384 + 256 * (ids % 8000)  # offset_bytes: a three-byte varint
+    a[:, 152] = 0x18
+    a[:, 153] = (off & 0x7F) | 0x80
+    a[:, 154] = ((off >> 7) & 0x7F) | 0x80
+    a[:, 155] = off >> 14
+    a[:, 156:159] = (0x20, 0x80, 0x02)  # size_bytes 256
+    d = np.zeros((n, 41), dtype=np.uint8)
+    d[:, 0] = 33
+    d[:, 8:10] = (0x0A, 20)
+    path_cols(d, 10)
+    d[:, 30:41] = np.frombuffer(bytes([0x1A, 9, 0x0A, 7]) + b"default", dtype=np.uint8)
+    return (PF.index_decode_host(d.tobytes()), PF.index_decode_host(a.tobytes()),
+            a[0].tobytes())
+
+
+def merge_rows(args):
+    import time
+
+    from oracle import fileset as OF
+    from pfs_amd import fileset as PF
+    rows = []
+    shapes = []
+    n2 = 524_288
+    perm = np.random.default_rng(1).permutation(2 * n2)  # which fileset holds file i
+    shapes.append(("two filesets of 524,288 files", [np.sort(perm[:n2]), np.sort(perm[n2:])]))
+    n10, shared = 104_858, 10_486
+    own = n10 - shared
+    perm = np.random.default_rng(2).permutation(10 * own + shared)
+    shapes.append(("ten filesets of 104,858 files, 10,486 of them in every fileset",
+                   [np.sort(np.concatenate([perm[:shared],
+                                            perm[shared + k * own:shared + (k + 1) * own]]))
+                    for k in range(10)]))
+    c = Chunker(ChunkParams(), 0)
+    keys = ["upload_ms", "rank_group_ms", "emit_ms", "d2h_ms"]
+    for name, id_sets in shapes:
+        pairs = []
+        for k, ids in enumerate(id_sets):
+            assert len(np.unique(ids)) == len(ids)
+            dele, add, frame = synthetic_lists(ids, 100 + k)
+            assert len(dele) == len(add) == len(ids)
+            pairs.append((dele, add))
+        m = OF._msgs()["Index"].FromString(frame[8:])  # the hand-built frame is what protobuf reads
+        assert m.path.startswith("/bench/d") and m.file.tag == "default" and \
+            m.file.data_refs[0].size_bytes == 256 and m.file.data_refs[0].ref.size_bytes == 8_000_000
+        row = {"shape": name, "filesets": len(pairs), "streams": 2 * len(pairs),
+               "reps": args.reps, "warmup": args.warmup}
+        for deletive in (False, True):
+            runs = {1: [], 0: []}
+            want = None
+            for i in range(args.warmup + args.reps):
+                for arm in (1, 0):
+                    _lib.set_knob("PFSCDC_INDEX_MERGE", arm)
+                    t0 = time.perf_counter()
+                    lst = PF.index_merge(pairs, chunker=c, deletive=deletive)
+                    wall = (time.perf_counter() - t0) * 1e3
+                    stats = PF.last_merge_stats(c)
+                    if stats["device"] != arm:
+                        raise SystemExit("read_bench: the other arm ran")
+                    arrs = list_arrays(lst)
+                    if want is None:
+                        want = arrs
+                    elif arrs != want:
+                        raise SystemExit("read_bench: the arms' lists differ")
+                    lst.free()
+                    if i >= args.warmup:
+                        stats["wall_ms"] = wall
+                        runs[arm].append(stats)
+            mode = {}
+            for arm, an in ((1, "device"), (0, "host")):
+                r = runs[arm]
+                mode[an] = {k: {"median": round(statistics.median(x[k] for x in r), 3),
+                                "min": round(min(x[k] for x in r), 3),
+                                "max": round(max(x[k] for x in r), 3)} for k in keys + ["wall_ms"]}
+                mode[an].update({k: r[0][k] for k in ("entries_in", "groups", "entries_out")})
+            mode["lists_equal"] = True
+            row["deletive" if deletive else "files"] = mode
+        _lib.set_knob("PFSCDC_INDEX_MERGE", _lib.knob_info()["PFSCDC_INDEX_MERGE"][2])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del pairs
+    c.close()
+    return rows
+
+
+def compact_rows(args):
+    """One compaction of a commit of two filesets, stage by stage."""
+    import time
+
+    from pfs_amd import chunk as pc
+    from pfs_amd import fileset as PF
+    nfiles, fbytes = args.files, 256
+    store = pc.ChunkStore()
+    st = PF.Storage(0, ChunkParams(), store=store)
+    data = np.random.default_rng(nfiles).integers(0, 256, nfiles * fbytes + 64, dtype=np.uint8)
+    infos = []
+    t0 = time.perf_counter()
+    for half in (0, 1):  # the second fileset: the odd files again, and every 16th file deleted
+        w = st.new_unordered_writer()
+        for i in range(half, nfiles, 1 + half):
+            w.put("/bench/d%03d/f%07d" % (i >> 12, i), "", False, data[i * fbytes:(i + 1) * fbytes])
+        if half:
+            for i in range(0, nfiles, 16):
+                w.delete("/bench/d%03d/f%07d" % (i >> 12, i), "")
+        infos += w.close()
+        w.release()
+    write_s = time.perf_counter() - t0
+    assert len(infos) == 2
+    row = {"files": nfiles, "file_bytes": fbytes, "filesets": 2, "write_s": round(write_s, 2),
+           "index_merge_knob": _lib.get_knob("PFSCDC_INDEX_MERGE"),
+           "note": "copies_ms includes the Python event callback (one call per index entry "
+                   "and chunk)"}
+    c = Chunker(ChunkParams(), 0)
+    t0 = time.perf_counter()
+    pairs = [(PF.index_read(c, store, i.deletive), PF.index_read(c, store, i.additive)) for i in infos]
+    t1 = time.perf_counter()
+    deletes = PF.index_merge(pairs, chunker=c, deletive=True)
+    files = PF.index_merge(pairs, chunker=c)
+    merge_stats = PF.last_merge_stats(c)
+    t2 = time.perf_counter()
+    before = len(store)
+    w = st.new_writer()
+    w.copy_lists(files, deletes)
+    t3 = time.perf_counter()
+    prim = w.close()
+    t4 = time.perf_counter()
+    data_ev = [e for e in w.events if e[0] == "chunk" and e[1] == -1]
+    cheap = sum(e[3] for e in data_ev if e[6])
+    row.update({
+        "index_reads_ms": round((t1 - t0) * 1e3, 1), "merge_ms": round((t2 - t1) * 1e3, 1),
+        "merge_files_stats": merge_stats, "copies_ms": round((t3 - t2) * 1e3, 1),
+        "close_ms": round((t4 - t3) * 1e3, 1),
+        "files_out": prim.num_files, "deletes_out": prim.num_deletes, "size_bytes": prim.size_bytes,
+        "cheap_copied_bytes": int(cheap), "rerolled_bytes": int(prim.size_bytes - cheap),
+        "data_chunks_cheap": sum(1 for e in data_ev if e[6]),
+        "data_chunks_formed": sum(1 for e in data_ev if not e[6]),
+        "index_chunks_formed": sum(1 for e in w.events if e[0] == "chunk" and e[1] >= 0),
+        "new_store_objects": len(store) - before})
+    w.release()
+    got = st.open([prim])
+    want = st.open(infos)
+    row["reads_back_as_its_inputs"] = got._list.raw() is not None and \
+        [(f.path, f.size_bytes) for f in got.files()[:2000]] == \
+        [(f.path, f.size_bytes) for f in want.files()[:2000]] and len(got._list) == len(want._list)
+    c.close()
+    print(json.dumps(row), flush=True)
+    return [row]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--index", action="store_true")
+    ap.add_argument("--merge", action="store_true")
+    ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--files", type=int, default=1 << 20)
     ap.add_argument("--tar", action="store_true")
     ap.add_argument("--chunks", type=int, default=1024)
     ap.add_argument("--chunk-bytes", type=int, default=4 << 20)
@@ -244,6 +441,17 @@ def main():
             else os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("read_bench: needs a GPU")
+    if args.merge or args.compact:
+        what = "merge" if args.merge else "compact"
+        if args.out == os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json"):
+            args.out = os.path.join(ROOT, "profiles", "r10", "compact", what + ".json")
+        rows = merge_rows(args) if args.merge else compact_rows(args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/read_bench.py --" + what,
+                       "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
+            f.write("\n")
+        return
     if args.index:
         if args.out == os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json"):
             args.out = os.path.join(ROOT, "profiles", "r9", "index_read", "index_read.json")
