@@ -816,6 +816,79 @@ int pfscdc_last_merge_stats(pfscdc_ctx* ctx, uint64_t out[4]);
  * strings, DataRef copy), out[3] the copy of the list to the host. */
 int pfscdc_last_merge_timings(pfscdc_ctx* ctx, float out[4]);
 
+/* ---- index lists that stay on the device (no reference counterpart: a GPU-side hand-over) ----
+ * pfscdc_index_read copies each decoded list to the host, pfscdc_index_merge_ctx uploads the lists
+ * again and copies the result back, and pfscdc_store_read_tar reads every DataRef on the host to
+ * plan its window.  A pfscdc_dev_list owns the same three arrays (pfscdc_index_entry, the string
+ * blob, pfscdc_full_dataref) in the formats the decode and merge kernels write, on the ctx's
+ * device; only the counts are on the host.  Read, merge and tar over such lists move nothing per
+ * file or per DataRef across the host link.  A handle is bound to the device of the ctx that made
+ * it (PFSCDC_EINVAL with a ctx of another device) and is owned by one thread at a time. */
+typedef struct pfscdc_dev_list pfscdc_dev_list;
+/* A resident copy of a host list, and back: the downloaded list equals the uploaded one array for
+ * array. */
+int pfscdc_dev_list_upload(pfscdc_ctx* ctx, const pfscdc_index_list* l, pfscdc_dev_list** out);
+int pfscdc_dev_list_download(pfscdc_ctx* ctx, const pfscdc_dev_list* d, pfscdc_index_list** out);
+uint32_t pfscdc_dev_list_count(const pfscdc_dev_list* d);
+uint32_t pfscdc_dev_list_num_datarefs(const pfscdc_dev_list* d);
+uint64_t pfscdc_dev_list_blob_len(const pfscdc_dev_list* d);
+int pfscdc_dev_list_free(pfscdc_dev_list* d);
+/* pfscdc_index_read with a resident result.  With no filter (NULL, or every member unset) and the
+ * PFSCDC_INDEX_DECODE knob at 1, the levels above 0 are read as pfscdc_index_read reads them
+ * (small lists the host selection needs) and the level of File entries stays where the decode
+ * kernels wrote it: nothing of it is copied out, and pfscdc_last_index_timings' out[4] covers the
+ * upper levels only.  With a filter that names a part, with the knob at 0, for an empty root and
+ * for a root that is itself a level-0 entry the call is pfscdc_index_read followed by
+ * pfscdc_dev_list_upload (a level-0 selection on the device is not built);
+ * pfscdc_last_resident_stats tells which.  Errors as pfscdc_index_read's. */
+int pfscdc_index_read_dev(pfscdc_ctx* ctx, const pfscdc_store* store, const void* root,
+                          uint64_t root_len, const pfscdc_index_filter* filter,
+                          pfscdc_dev_list** out);
+/* Both modes of pfscdc_index_merge_ctx over resident lists (lists as that call takes them; NULL =
+ * an empty list) with a resident result: the streams are gathered by device-to-device copies, the
+ * merge kernels run as they do for pfscdc_index_merge_ctx, and their output arrays become the new
+ * list.  The PFSCDC_INDEX_MERGE knob does not govern this call: resident inputs mean the device
+ * arm.  A stream that is not strictly ascending, or more than 2^32 - 1 entries or DataRef records
+ * in, is downloaded, merged by the host function of the mode and uploaded;
+ * pfscdc_last_merge_stats' out[0] is then 0.  pfscdc_last_merge_timings: out[0] the gather (host
+ * arm: the upload of the result), out[3] the guards' copy alone (host arm: the download of the
+ * inputs). */
+int pfscdc_index_merge_dev(pfscdc_ctx* ctx, int mode, const pfscdc_dev_list* const* lists,
+                           uint32_t nfilesets, pfscdc_dev_list** out);
+/* pfscdc_tar_layout for a resident list: *total the stream's length, entry_offsets (nullable,
+ * count + 1 entries) as pfscdc_tar_layout's.  Runs the plan stage of pfscdc_dev_list_read_tar if
+ * the handle has none yet (kernels: every DataRef's size and validity, prefix sums, per entry the
+ * name rules above and the span, prefix sums of the spans) and caches it in the handle; errors as
+ * pfscdc_dev_list_read_tar's name and size errors. */
+int pfscdc_dev_list_tar_layout(pfscdc_ctx* ctx, pfscdc_dev_list* d, uint64_t* total,
+                               uint64_t* entry_offsets);
+/* pfscdc_store_read_tar over a resident list: the same window rules, the same bytes, the same
+ * error codes (PFSCDC_ENOTFOUND and PFSCDC_ECORRUPT before anything is written to out;
+ * PFSCDC_EUNSUPPORTED / PFSCDC_EINVAL with the lowest refused file named in pfscdc_last_error,
+ * PFSCDC_EINVAL for a DataRef that reaches past its chunk).  Per call, on the device: the entries
+ * that meet the window are found by searches in the cached offsets; every DataRef of theirs is
+ * clipped to the window, one lane each, and the non-empty pieces are counted, prefix-summed and
+ * written as the dense slice arrays the gather kernel takes; a piece whose DataRef before it gave
+ * none, or names another chunk or another Ref.SizeBytes of the same chunk, heads a run, and only the
+ * runs' {id, dek, size} records (80 bytes each) come to the host, which looks their chunks up in
+ * the store, holds each stored length against the run's size, deduplicates them by id and sends
+ * back one chunk number per run; the kernel that applies it checks every slice against its
+ * chunk's stored length once more, since the gather checks nothing (PFSCDC_ECORRUPT).  A path is
+ * read up to its first NUL, as the host call reads it.  The tar entries are the plan's own records with the
+ * list's blob as the name table.  Refused with PFSCDC_EUNSUPPORTED: a list whose entries do not
+ * hold their DataRefs at [first, first + count) packed in entry order (every list this library
+ * makes does), and a blob of 4 GiB or more.  Every array the planning kernels fill ends in a
+ * 64-byte guard that the call checks (PFSCDC_EHIP). */
+int pfscdc_dev_list_read_tar(pfscdc_ctx* ctx, const pfscdc_store* store, pfscdc_dev_list* d,
+                             uint64_t begin, uint64_t len, void* out, uint64_t out_cap,
+                             int out_on_device, uint64_t* nwritten);
+/* Counts of the last resident calls on ctx: out[0] 1 the last pfscdc_index_read_dev kept the
+ * decode's device arrays, 0 it uploaded the host path's list, out[1] the bytes it uploaded;
+ * of the last pfscdc_dev_list_read_tar: out[2] runs, out[3] distinct chunks, out[4] non-empty
+ * pieces, out[5] bytes copied device to host (the window into a host out not counted), out[6]
+ * bytes copied host to device except chunk ciphertext, out[7] 1 the cached plan was reused. */
+int pfscdc_last_resident_stats(pfscdc_ctx* ctx, uint64_t out[8]);
+
 /* shard (fileset/shard.go:27-49) over a merged list: cb receives each shard's path range
  * (lower, upper; "" = an open end).  A range is closed in front of the first file that finds
  * threshold or more content bytes collected (the test comes before the file is added); its upper

@@ -74,6 +74,10 @@ EXPORTED = [
     "pfscdc_fsw_create", "pfscdc_fsw_delete", "pfscdc_fsw_copy", "pfscdc_fsw_copy_lists",
     "pfscdc_fsw_copy_filesets", "pfscdc_fsw_close", "pfscdc_fsw_fileset",
     "pfscdc_fsw_last_error", "pfscdc_fsw_destroy",
+    "pfscdc_dev_list_upload", "pfscdc_dev_list_download", "pfscdc_dev_list_count",
+    "pfscdc_dev_list_num_datarefs", "pfscdc_dev_list_blob_len", "pfscdc_dev_list_free",
+    "pfscdc_index_read_dev", "pfscdc_index_merge_dev", "pfscdc_dev_list_tar_layout",
+    "pfscdc_dev_list_read_tar", "pfscdc_last_resident_stats",
 ]
 
 
@@ -360,6 +364,17 @@ def load() -> C.CDLL:
             "pfscdc_fsw_fileset": (i32, [vp, P(FilesetInfo)]),
             "pfscdc_fsw_last_error": (C.c_char_p, [vp]),
             "pfscdc_fsw_destroy": (i32, [vp]),
+            "pfscdc_dev_list_upload": (i32, [vp, vp, P(vp)]),
+            "pfscdc_dev_list_download": (i32, [vp, vp, P(vp)]),
+            "pfscdc_dev_list_count": (u32, [vp]),
+            "pfscdc_dev_list_num_datarefs": (u32, [vp]),
+            "pfscdc_dev_list_blob_len": (u64, [vp]),
+            "pfscdc_dev_list_free": (i32, [vp]),
+            "pfscdc_index_read_dev": (i32, [vp, vp, vp, u64, P(IndexFilter), P(vp)]),
+            "pfscdc_index_merge_dev": (i32, [vp, i32, P(vp), u32, P(vp)]),
+            "pfscdc_dev_list_tar_layout": (i32, [vp, vp, P(u64), P(u64)]),
+            "pfscdc_dev_list_read_tar": (i32, [vp, vp, vp, u64, u64, vp, u64, i32, P(u64)]),
+            "pfscdc_last_resident_stats": (i32, [vp, P(u64)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

@@ -3041,4 +3041,318 @@ hipError_t launch_merge_copy(const MrgIn& in, const MrgCopy* copy, pfscdc_full_d
   return hipGetLastError();
 }
 
+// ---- 10. GetFileTAR over a device-resident list ------------------------------------------------
+// tar_plan (tar.cpp) restated for a list whose entries, strings and DataRefs lie on the device, so
+// that a window renders with nothing per file or per DataRef crossing to the host.
+//
+// Plan, once per list:
+//  10a sizes    one lane per DataRef: StoreBatch::valid's rule, dsz[k] = SizeBytes.
+//  10b scan     dpre = prefix sums of dsz (one workgroup, index_scan_kernel's shape, the add
+//               saturating at kRtarCap so no sum wraps): a file's size is a difference of two
+//               prefixes, whatever its DataRef count, and a piece's place in its file another.
+//  10c entries  one lane per entry: the packed layout (first = the first + count of the entry
+//               before, the last ends at nr) so that a DataRef's file is found by a search;
+//               tar_name_check over the path in the blob; the TarEntry record (name_off =
+//               path_off: the blob is the name table) and the span.  The lowest refused entry
+//               and its reason leave through one atomic minimum.
+//  10b again    offsets = prefix sums of the spans, written into the TarEntry records as well.
+// Window, per call:
+//  10d window   one lane: the entries [i0, i1) that meet [begin, end) by two searches in the
+//               offsets, and their DataRefs [k0, k1).
+//  10e pieces   one lane per DataRef of [k0, k1) (a 300-DataRef file is 300 lanes, not a loop):
+//               its file by a search in the entries' first (the last entry with first <= k, which
+//               skips entries of count 0), its place p = off + 512 + dpre[k] - dpre[first], the
+//               clip to the window as TarPiece.  A non-empty piece is a run head when the DataRef
+//               before it gave no piece or names another chunk or another size of it.  Count pass, merge_scan_kernel
+//               over {piece, head, keystream blocks}, fill pass: the dense arrays
+//               chacha_slice_gather_kernel takes, slice.chunk = the run's number, and one record
+//               per run for the host, which alone knows the store.
+//  10f chunks   slice.chunk = table[run] once the host has looked the runs' chunks up, and each
+//               slice held against its chunk's stored length: the gather checks no bounds.
+// Every kernel strides; widths as §9's (merge_grid: capped by the PFSCDC_CHACHA_GRID knob).
+
+// What kind of level a decoded list is, without the list leaving the device: flags[0] |= and
+// flags[1] &= every entry's flags (a wave reduces first; one atomic pair per wave).
+__global__ __launch_bounds__(kIdxBlock) void index_flags_kernel(
+    const pfscdc_index_entry* __restrict__ entries, uint64_t n, uint32_t* __restrict__ flags) {
+  uint32_t any = 0, all = ~0u;
+  for (uint64_t i = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; i < n;
+       i += (uint64_t)gridDim.x * kIdxBlock) {
+    any |= entries[i].flags;
+    all &= entries[i].flags;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    any |= (uint32_t)__shfl_xor((int)any, o, 64);
+    all &= (uint32_t)__shfl_xor((int)all, o, 64);
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    atomicOr(&flags[0], any);
+    atomicAnd(&flags[1], all);
+  }
+}
+
+hipError_t launch_index_flags(const pfscdc_index_entry* entries, uint64_t n, uint32_t* flags,
+                              int num_cus, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  index_flags_kernel<<<merge_grid(n, num_cus), kIdxBlock, 0, st>>>(entries, n, flags);
+  return hipGetLastError();
+}
+
+PFS_DEV uint64_t rtar_sat_add(uint64_t a, uint64_t b) {  // a, b <= kRtarCap
+  const uint64_t s = a + b;
+  return s < kRtarCap ? s : kRtarCap;
+}
+
+__global__ __launch_bounds__(kIdxBlock) void rtar_sizes_kernel(
+    const pfscdc_full_dataref* __restrict__ drs, uint64_t nr, uint64_t* __restrict__ dsz,
+    uint32_t* __restrict__ bad) {
+  for (uint64_t k = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; k < nr;
+       k += (uint64_t)gridDim.x * kIdxBlock) {
+    const int64_t rs = drs[k].ref_size, ob = drs[k].data.offset_bytes, sb = drs[k].data.size_bytes;
+    const bool ok = rs >= 0 && ob >= 0 && sb >= 0 && ob <= rs && sb <= rs - ob;
+    if (!ok) atomicOr(bad, 1u);
+    dsz[k] = !ok ? 0 : (uint64_t)sb < kRtarCap ? (uint64_t)sb : kRtarCap;
+  }
+}
+
+__global__ __launch_bounds__(kIdxScanBlock) void rtar_scan_kernel(
+    const uint64_t* __restrict__ in, uint64_t n, uint64_t* __restrict__ out,
+    TarEntry* __restrict__ ent) {
+  __shared__ uint64_t a[kIdxScanBlock];
+  const uint32_t t = threadIdx.x;
+  uint64_t carry = 0;
+  for (uint64_t f0 = 0; f0 < n; f0 += kIdxScanBlock) {
+    const uint64_t f = f0 + t;
+    a[t] = f < n ? in[f] : 0;
+    __syncthreads();
+    for (uint32_t d = 1; d < kIdxScanBlock; d <<= 1) {
+      const uint64_t x = t >= d ? a[t - d] : 0;
+      __syncthreads();
+      a[t] = rtar_sat_add(a[t], x);
+      __syncthreads();
+    }
+    if (f < n) {  // exclusive: the inclusive sum of the lane before
+      const uint64_t v = rtar_sat_add(carry, t ? a[t - 1] : 0);
+      out[f] = v;
+      if (ent) ent[f].off = v;
+    }
+    const uint64_t next = rtar_sat_add(carry, a[kIdxScanBlock - 1]);
+    __syncthreads();
+    carry = next;
+  }
+  if (t == 0) out[n] = carry;
+}
+
+__global__ __launch_bounds__(kIdxBlock) void rtar_entries_kernel(
+    RtarList l, const uint64_t* __restrict__ dpre, TarEntry* __restrict__ ent,
+    uint64_t* __restrict__ span, unsigned long long* __restrict__ err) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; i < l.n;
+       i += (uint64_t)gridDim.x * kIdxBlock) {
+    const pfscdc_index_entry e = l.entries[i];
+    const uint64_t first = e.first, count = e.count;
+    uint64_t len = e.path_len;
+    uint32_t why = 0;
+    uint64_t z = 0;
+    int32_t split = -1;
+    if (first > l.nr || count > l.nr - first) {
+      why = kRtarBeyond;
+    } else {
+      const uint64_t want = i ? (uint64_t)l.entries[i - 1].first + l.entries[i - 1].count : 0;
+      if (first != want || (i + 1 == l.n && first + count != l.nr)) why = kRtarNotPacked;
+    }
+    if (!why && (e.path_off > l.nb || len >= l.nb - e.path_off)) why = kRtarString;
+    if (!why) {
+      const uint64_t hi = dpre[first + count];
+      z = hi - dpre[first];
+      if (hi >= kRtarCap) why = kRtarOverflow;
+    }
+    if (!why) {  // tar_name_check, then tar_plan's directory rule
+      const uint8_t* name = (const uint8_t*)l.blob + e.path_off;
+      // the host reads the path as a C string: a path with a NUL inside ends there in both arms
+      for (uint64_t k = 0; k < len; k++)
+        if (name[k] == 0) len = k;
+      if (len == 0) {
+        why = kRtarEmpty;
+      } else if (name[len - 1] == '/' && z) {
+        why = kRtarDirContent;
+      } else {
+        for (uint64_t k = 0; k < len && !why; k++)
+          if (name[k] >= 0x80) why = kRtarNotAscii;
+        if (!why && z > kTarMaxSize) why = kRtarTooBig;
+        if (!why && len > 100) {  // splitUSTARPath
+          uint64_t lim = len < 156 ? len : 156;
+          if (len <= 156 && name[len - 1] == '/') lim = len - 1;
+          uint64_t k = lim;
+          while (k > 0 && name[k - 1] != '/') k--;
+          if (k < 2 || len - k > 100 || len - k == 0 || k - 1 > 155) why = kRtarNoSplit;
+          else split = (int32_t)(k - 1);
+        }
+        if (!why && name[len - 1] == '/' && count) why = kRtarDirPieces;
+      }
+    }
+    if (why) atomicMin(err, (unsigned long long)(i << 8 | why));
+    ent[i] = TarEntry{0, z, (uint32_t)e.path_off, (uint16_t)len, (int16_t)split};
+    span[i] = why ? 0 : 512 + ((z + 511) & ~511ull);
+  }
+}
+
+__global__ void rtar_window_kernel(RtarList l, const uint64_t* __restrict__ off, uint64_t begin,
+                                   uint64_t end, RtarWindow* __restrict__ w) {
+  if (blockIdx.x || threadIdx.x) return;
+  uint64_t lo = 0, hi = l.n + 1;  // the first i of off[0, n] with off[i] > begin
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (off[mid] > begin) hi = mid;
+    else lo = mid + 1;
+  }
+  const uint64_t i0 = lo ? lo - 1 : 0;  // the entry (or the trailer, i0 = n) that holds begin
+  lo = i0 < l.n ? i0 : l.n;
+  hi = l.n;  // the first i >= i0 of off[0, n) with off[i] >= end
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (off[mid] >= end) hi = mid;
+    else lo = mid + 1;
+  }
+  RtarWindow r{i0 < l.n ? i0 : l.n, lo, 0, 0};
+  if (r.i0 < r.i1) {
+    r.k0 = l.entries[r.i0].first;
+    r.k1 = (uint64_t)l.entries[r.i1 - 1].first + l.entries[r.i1 - 1].count;
+  }
+  *w = r;
+}
+
+struct RtarClip {
+  uint64_t offset, size, out_off;  // size 0: no piece
+};
+// DataRef k of the window's entries, clipped as TarPiece (tar_plan)
+PFS_DEV RtarClip rtar_clip(const RtarPieces& p, uint64_t k) {
+  uint64_t lo = p.w.i0, hi = p.w.i1;  // the last entry with first <= k
+  while (hi - lo > 1) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (p.l.entries[mid].first <= k) lo = mid;
+    else hi = mid;
+  }
+  const uint64_t at = p.ent[lo].off + 512 + (p.dpre[k] - p.dpre[p.l.entries[lo].first]);
+  const uint64_t sz = p.dpre[k + 1] - p.dpre[k];
+  const uint64_t a = at > p.begin ? at : p.begin, b = at + sz < p.end ? at + sz : p.end;
+  if (a >= b) return RtarClip{0, 0, 0};
+  return RtarClip{(uint64_t)p.l.drs[k].data.offset_bytes + (a - at), b - a, a - p.begin};
+}
+
+// Same Ref.Id and same Ref.SizeBytes: the host compares a run's ref_size with the stored
+// chunk's length once, for its head, so a DataRef that claims another size for the same id must
+// head a run of its own (StoreBatch::add then refuses it as pfscdc_store_read_tar does).
+PFS_DEV bool rtar_same_chunk(const pfscdc_full_dataref* a, const pfscdc_full_dataref* b) {
+  const uint64_t *x = (const uint64_t*)a->ref.id, *y = (const uint64_t*)b->ref.id;
+  return x[0] == y[0] && x[1] == y[1] && x[2] == y[2] && x[3] == y[3] &&
+         a->ref_size == b->ref_size;
+}
+
+__global__ __launch_bounds__(kIdxBlock) void rtar_pieces_kernel(
+    RtarPieces p, MrgCount* __restrict__ cnt, const uint64_t* __restrict__ base,
+    pfscdc_slice* __restrict__ slices, uint64_t* __restrict__ out_off,
+    uint64_t* __restrict__ blk_base, RtarRun* __restrict__ runs) {
+  const uint64_t nk = p.w.k1 - p.w.k0;
+  for (uint64_t q = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; q < nk;
+       q += (uint64_t)gridDim.x * kIdxBlock) {
+    const uint64_t k = p.w.k0 + q;
+    const RtarClip c = rtar_clip(p, k);
+    MrgCount x{0, 0, 0};
+    if (c.size) {
+      x.emit = 1;
+      x.blob = (c.offset + c.size - 1) / 64 - c.offset / 64 + 1;
+      x.recs = q == 0 || !rtar_same_chunk(&p.l.drs[k], &p.l.drs[k - 1]) ||
+               rtar_clip(p, k - 1).size == 0;
+    }
+    if (!slices) {
+      cnt[q] = x;
+      continue;
+    }
+    if (q == 0) {  // the arrays' last entries: the totals
+      const uint64_t m = base[3 * nk];
+      out_off[m] = p.end - p.begin;
+      blk_base[m] = base[3 * nk + 2];
+    }
+    if (!c.size) continue;
+    const uint64_t j = base[3 * q], r = base[3 * q + 1] + x.recs - 1;
+    if (base[3 * q + 3] - j != 1) continue;  // (never: the count pass's clip)
+    slices[j] = pfscdc_slice{(uint32_t)r, 0, c.offset, c.size};
+    out_off[j] = c.out_off;
+    blk_base[j] = base[3 * q + 2];
+    if (x.recs) {
+      const pfscdc_full_dataref* dr = &p.l.drs[k];
+      RtarRun run;
+      run.ref = dr->ref;
+      run.ref_size = dr->ref_size;
+      run.first_piece = (uint32_t)j;
+      run.reserved = 0;
+      runs[r] = run;
+    }
+  }
+}
+
+// The gather checks no bounds, so the last word before it is said here: a slice that does not
+// lie inside its chunk's stored bytes (chunk_offs: the batch's nchunks + 1 offsets) sets *bad.
+__global__ __launch_bounds__(kIdxBlock) void rtar_chunks_kernel(
+    pfscdc_slice* __restrict__ slices, uint64_t m, const uint32_t* __restrict__ table,
+    const uint64_t* __restrict__ chunk_offs, uint32_t nchunks, uint32_t* __restrict__ bad) {
+  for (uint64_t j = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; j < m;
+       j += (uint64_t)gridDim.x * kIdxBlock) {
+    const pfscdc_slice sl = slices[j];
+    const uint32_t c = table[sl.chunk];
+    bool ok = c < nchunks;
+    if (ok) {
+      const uint64_t len = chunk_offs[c + 1] - chunk_offs[c];
+      ok = sl.offset <= len && sl.size <= len - sl.offset;
+    }
+    if (!ok) atomicOr(bad, 1u);
+    slices[j].chunk = ok ? c : 0u;
+  }
+}
+
+hipError_t launch_rtar_sizes(const pfscdc_full_dataref* drs, uint64_t nr, uint64_t* dsz,
+                             uint32_t* bad, int num_cus, hipStream_t st) {
+  if (nr == 0) return hipSuccess;
+  rtar_sizes_kernel<<<merge_grid(nr, num_cus), kIdxBlock, 0, st>>>(drs, nr, dsz, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtar_scan(const uint64_t* in, uint64_t n, uint64_t* out, TarEntry* ent,
+                            hipStream_t st) {
+  rtar_scan_kernel<<<1, kIdxScanBlock, 0, st>>>(in, n, out, ent);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtar_entries(const RtarList& l, const uint64_t* dpre, TarEntry* ent,
+                               uint64_t* span, unsigned long long* err, int num_cus,
+                               hipStream_t st) {
+  if (l.n == 0) return hipSuccess;
+  rtar_entries_kernel<<<merge_grid(l.n, num_cus), kIdxBlock, 0, st>>>(l, dpre, ent, span, err);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtar_window(const RtarList& l, const uint64_t* off, uint64_t begin, uint64_t end,
+                              RtarWindow* w, hipStream_t st) {
+  rtar_window_kernel<<<1, 64, 0, st>>>(l, off, begin, end, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtar_pieces(const RtarPieces& p, MrgCount* cnt, const uint64_t* base,
+                              pfscdc_slice* slices, uint64_t* out_off, uint64_t* blk_base,
+                              RtarRun* runs, int num_cus, hipStream_t st) {
+  if (p.w.k1 <= p.w.k0) return hipSuccess;
+  rtar_pieces_kernel<<<merge_grid(p.w.k1 - p.w.k0, num_cus), kIdxBlock, 0, st>>>(
+      p, cnt, base, slices, out_off, blk_base, runs);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtar_chunks(pfscdc_slice* slices, uint64_t m, const uint32_t* table,
+                              const uint64_t* chunk_offs, uint32_t nchunks, uint32_t* bad, int num_cus,
+                              hipStream_t st) {
+  if (m == 0) return hipSuccess;
+  rtar_chunks_kernel<<<merge_grid(m, num_cus), kIdxBlock, 0, st>>>(slices, m, table, chunk_offs,
+                                                                    nchunks, bad);
+  return hipGetLastError();
+}
+
 }  // namespace pfscdc

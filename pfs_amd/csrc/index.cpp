@@ -1,6 +1,8 @@
 // index.cpp — reading a fileset back: index.Reader.Iterate over a chunk store and
 // MergeReader.iterate (host logic; the frame walk and entry decode kernels are in
-// cdc_kernels.hip, the proto parser both sides share in index_parse.h).
+// cdc_kernels.hip, the proto parser both sides share in index_parse.h).  Both also with a
+// device-resident result (pfscdc_index_read_dev, pfscdc_index_merge_dev: the decode's and the
+// merge's output arrays become a pfscdc_dev_list, dev_list.h, instead of being copied out).
 //
 // Reference (paths under /root/reference/src/internal):
 //   storage/fileset/index/reader.go:41-83    Iterate: levels, atEnd / atStart / tag
@@ -16,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_list.h"
 #include "index_list.h"
 #include "pfscdc_internal.h"
 
@@ -95,7 +98,8 @@ int corrupt(pfscdc_ctx* ctx, uint32_t level, uint64_t offset) {
 // open_end: the selection ends before the level does (its last chunk is the tail chunk).
 int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, uint64_t n,
                         const std::vector<uint64_t>& cb, const std::vector<int64_t>& off,
-                        uint32_t nc, bool open_end, List* out) {
+                        uint32_t nc, bool open_end, List* out, pfscdc_dev_list* keep = nullptr,
+                        bool* kept = nullptr) {
   IndexStats& st = ctx_index_stats(ctx);
   hipStream_t s = ctx_stream(ctx);
   const int cus = ctx_num_cus(ctx);
@@ -186,6 +190,28 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
                                  d_drs.as<pfscdc_full_dataref>(), d_blob.as<char>(), cus, s));
   IDX_HIP(ctx, hipStreamSynchronize(s));
   st.ms[3] += ms_since(t0);
+  if (keep) {  // a level of File entries only is level 0: its arrays are the resident list
+    t0 = Clock::now();
+    DevMem d_flags;
+    uint32_t flags[2] = {0, ~0u};  // OR and AND of the entries' flags
+    IDX_HIP(ctx, d_flags.alloc(sizeof flags));
+    IDX_HIP(ctx, hipMemcpyAsync(d_flags.p, flags, sizeof flags, hipMemcpyHostToDevice, s));
+    IDX_HIP(ctx, launch_index_flags(d_entries.as<pfscdc_index_entry>(), nf, d_flags.as<uint32_t>(),
+                                    cus, s));
+    IDX_HIP(ctx, hipMemcpyAsync(flags, d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
+    IDX_HIP(ctx, hipStreamSynchronize(s));
+    if (!(flags[0] & PFSCDC_IDX_HAS_RANGE)) {
+      std::swap(keep->entries, d_entries.p);
+      std::swap(keep->drs, d_drs.p);
+      std::swap(keep->blob, d_blob.p);
+      keep->n = nf;
+      keep->nr = totals[0];
+      keep->nb = totals[1];
+      *kept = true;
+    }
+    st.ms[3] += ms_since(t0);  // the flags pass counts as decode time, kept or not
+    if (*kept) return PFSCDC_OK;
+  }
   // ---- the list to the host
   t0 = Clock::now();
   out->entries.resize(nf);
@@ -205,7 +231,8 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
 // The level below the entries parents of cur: their chunks through the read path into one
 // device buffer, then the decode (device, or host with the PFSCDC_INDEX_DECODE knob at 0).
 int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const List& cur,
-               std::vector<uint32_t> parents, int64_t tail, List* out) {
+               std::vector<uint32_t> parents, int64_t tail, List* out,
+               pfscdc_dev_list* keep = nullptr, bool* kept = nullptr) {
   IndexStats& st = ctx_index_stats(ctx);
   if (tail >= 0) parents.push_back((uint32_t)tail);
   const uint32_t nc = (uint32_t)parents.size();
@@ -245,7 +272,8 @@ int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const
   st.n[0] += nc;
   st.n[2]++;
   if (knob(Knob::IndexDecode) != 0)
-    return decode_level_device(ctx, level, d_buf.as<uint8_t>(), n, cb, off, nc, tail >= 0, out);
+    return decode_level_device(ctx, level, d_buf.as<uint8_t>(), n, cb, off, nc, tail >= 0, out,
+                               keep, kept);
   // the host arm: the level's bytes to the host, then the specification's decode
   const uint64_t start0 = (uint64_t)off[0];
   auto t0 = Clock::now();
@@ -268,8 +296,17 @@ int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const
 // back with the list: a kernel that wrote past what the prefix sums counted fails the call.
 constexpr uint64_t kMrgGuard = 64;
 
-int merge_device(pfscdc_ctx* ctx, int mode, const List* const* lists, uint32_t ns, List* out,
-                 bool* ran) {
+// One input stream: its three arrays where they lie (host vectors, or a resident list's arrays).
+struct MrgSrc {
+  const void *entries = nullptr, *blob = nullptr, *drs = nullptr;
+  uint64_t n = 0, nb = 0, nr = 0;
+};
+
+// kind: where the streams lie (host to device, or device to device for resident lists).  keep
+// (nullable): the output arrays become this resident list and nothing but the guards is copied
+// to the host; else the list is copied into out.
+int merge_device(pfscdc_ctx* ctx, int mode, const MrgSrc* src, uint32_t ns, hipMemcpyKind kind,
+                 List* out, pfscdc_dev_list* keep, bool* ran) {
   MergeStats& st = ctx_merge_stats(ctx);
   *ran = false;
   std::vector<uint64_t> tab(3 * (uint64_t)ns + 1, 0);  // stream_begin[ns + 1], blob_base, dr_base
@@ -279,10 +316,9 @@ int merge_device(pfscdc_ctx* ctx, int mode, const List* const* lists, uint32_t n
     sb[s] = n;
     bb[s] = nb;
     db[s] = nr;
-    if (!lists[s]) continue;
-    n += lists[s]->entries.size();
-    nb += lists[s]->blob.size();
-    nr += lists[s]->drs.size();
+    n += src[s].n;
+    nb += src[s].nb;
+    nr += src[s].nr;
   }
   sb[ns] = n;
   st.n[1] = n;
@@ -306,17 +342,14 @@ int merge_device(pfscdc_ctx* ctx, int mode, const List* const* lists, uint32_t n
   IDX_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (n + 1)));
   IDX_HIP(ctx, hipMemcpyAsync(d_tab.p, tab.data(), sizeof(uint64_t) * tab.size(), hipMemcpyHostToDevice, s));
   for (uint32_t k = 0; k < ns; k++) {
-    const List* l = lists[k];
-    if (!l) continue;
-    if (!l->entries.empty())
-      IDX_HIP(ctx, hipMemcpyAsync(d_entries.as<pfscdc_index_entry>() + sb[k], l->entries.data(),
-                                  sizeof(pfscdc_index_entry) * l->entries.size(), hipMemcpyHostToDevice, s));
-    if (!l->blob.empty())
-      IDX_HIP(ctx, hipMemcpyAsync(d_blob.as<char>() + bb[k], l->blob.data(), l->blob.size(),
-                                  hipMemcpyHostToDevice, s));
-    if (!l->drs.empty())
-      IDX_HIP(ctx, hipMemcpyAsync(d_drs.as<pfscdc_full_dataref>() + db[k], l->drs.data(),
-                                  sizeof(pfscdc_full_dataref) * l->drs.size(), hipMemcpyHostToDevice, s));
+    const MrgSrc& l = src[k];
+    if (l.n)
+      IDX_HIP(ctx, hipMemcpyAsync(d_entries.as<pfscdc_index_entry>() + sb[k], l.entries,
+                                  sizeof(pfscdc_index_entry) * l.n, kind, s));
+    if (l.nb) IDX_HIP(ctx, hipMemcpyAsync(d_blob.as<char>() + bb[k], l.blob, l.nb, kind, s));
+    if (l.nr)
+      IDX_HIP(ctx, hipMemcpyAsync(d_drs.as<pfscdc_full_dataref>() + db[k], l.drs,
+                                  sizeof(pfscdc_full_dataref) * l.nr, kind, s));
   }
   IDX_HIP(ctx, hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
   IDX_HIP(ctx, hipStreamSynchronize(s));
@@ -366,12 +399,14 @@ int merge_device(pfscdc_ctx* ctx, int mode, const List* const* lists, uint32_t n
   // ---- the list to the host
   t0 = Clock::now();
   uint8_t guard[3][kMrgGuard];
-  out->entries.resize(totals[0]);
-  out->drs.resize(totals[1]);
-  out->blob.resize(totals[2]);
-  if (eb) IDX_HIP(ctx, hipMemcpyAsync(out->entries.data(), d_oe.p, eb, hipMemcpyDeviceToHost, s));
-  if (rb) IDX_HIP(ctx, hipMemcpyAsync(out->drs.data(), d_or.p, rb, hipMemcpyDeviceToHost, s));
-  if (totals[2]) IDX_HIP(ctx, hipMemcpyAsync(out->blob.data(), d_ob.p, totals[2], hipMemcpyDeviceToHost, s));
+  if (!keep) {
+    out->entries.resize(totals[0]);
+    out->drs.resize(totals[1]);
+    out->blob.resize(totals[2]);
+  }
+  if (!keep && eb) IDX_HIP(ctx, hipMemcpyAsync(out->entries.data(), d_oe.p, eb, hipMemcpyDeviceToHost, s));
+  if (!keep && rb) IDX_HIP(ctx, hipMemcpyAsync(out->drs.data(), d_or.p, rb, hipMemcpyDeviceToHost, s));
+  if (!keep && totals[2]) IDX_HIP(ctx, hipMemcpyAsync(out->blob.data(), d_ob.p, totals[2], hipMemcpyDeviceToHost, s));
   IDX_HIP(ctx, hipMemcpyAsync(guard[0], d_oe.as<char>() + eb, kMrgGuard, hipMemcpyDeviceToHost, s));
   IDX_HIP(ctx, hipMemcpyAsync(guard[1], d_ob.as<char>() + totals[2], kMrgGuard, hipMemcpyDeviceToHost, s));
   IDX_HIP(ctx, hipMemcpyAsync(guard[2], d_or.as<char>() + rb, kMrgGuard, hipMemcpyDeviceToHost, s));
@@ -380,8 +415,56 @@ int merge_device(pfscdc_ctx* ctx, int mode, const List* const* lists, uint32_t n
   for (auto& g : guard)
     for (uint8_t b : g)
       if (b != 0xA5) return ctx_fail(ctx, PFSCDC_EHIP, "index merge: a kernel wrote past its array");
+  if (keep) {
+    std::swap(keep->entries, d_oe.p);
+    std::swap(keep->drs, d_or.p);
+    std::swap(keep->blob, d_ob.p);
+    keep->n = totals[0];
+    keep->nr = totals[1];
+    keep->nb = totals[2];
+  }
   st.n[2] = heads;
   st.n[3] = totals[0];
+  return PFSCDC_OK;
+}
+
+// index.NewReader(chunks, topIdx, opts...).Iterate: the walk both read entry points share.  The
+// selected level-0 entries go to *result.  keep (nullable; only with a filter that selects
+// everything): a level of File entries stays on the device as keep's arrays, *kept is set and
+// *result stays empty.
+int read_index(pfscdc_ctx* ctx, const pfscdc_store* store, const void* root, uint64_t root_len,
+               const IdxFilter& f, std::unique_ptr<List>* result, pfscdc_dev_list* keep,
+               bool* kept) {
+  pfscdc::ctx_index_stats(ctx) = pfscdc::IndexStats();
+  if (!root || !root_len) return PFSCDC_OK;  // r.topIdx == nil
+  // topLevel(): the root as a stream of one entry
+  std::unique_ptr<List> cur(new List());
+  {
+    const uint8_t *b = (const uint8_t*)root, *e = b + root_len;
+    IdxFrame fr;
+    if (!pfscdc::idx_parse(b, e, &fr, nullptr, 0) || !idx_append_frame(cur.get(), fr, b, e))
+      return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT, "the root index does not parse");
+  }
+  for (uint32_t level = 0;; level++) {
+    std::vector<uint32_t> sel, parents;
+    int64_t tail = -1;
+    const char* why = nullptr;
+    if (!select(*cur, f, &sel, &parents, &tail, &why))
+      return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT,
+                              "index level " + std::to_string(level) + " (its parent): " + why);
+    if (!sel.empty()) {
+      if (sel.size() == cur->entries.size() && (*result)->entries.empty())
+        result->swap(cur);  // everything selected: the decoded list is the result
+      else
+        for (uint32_t i : sel) idx_append_entry(result->get(), *cur, cur->entries[i]);
+    }
+    if (parents.empty()) break;
+    if (level >= 64) return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT, "more than 64 index levels");
+    std::unique_ptr<List> next(new List());
+    if (int rc = read_level(ctx, store, level, *cur, parents, tail, next.get(), keep, kept)) return rc;
+    if (kept && *kept) break;
+    cur.swap(next);
+  }
   return PFSCDC_OK;
 }
 
@@ -401,7 +484,13 @@ int pfscdc_index_merge_ctx(pfscdc_ctx* ctx, int mode, const pfscdc_index_list* c
   if (pfscdc::knob(pfscdc::Knob::IndexMerge) != 0) {
     std::unique_ptr<List> l(new List());
     bool ran = false;
-    if (int rc = merge_device(ctx, mode, lists, ns, l.get(), &ran)) return rc;
+    std::vector<MrgSrc> src(ns);
+    for (uint32_t k = 0; k < ns; k++)
+      if (lists[k])
+        src[k] = MrgSrc{lists[k]->entries.data(), lists[k]->blob.data(), lists[k]->drs.data(),
+                        lists[k]->entries.size(), lists[k]->blob.size(), lists[k]->drs.size()};
+    if (int rc = merge_device(ctx, mode, src.data(), ns, hipMemcpyHostToDevice, l.get(), nullptr, &ran))
+      return rc;
     if (ran) {
       st.n[0] = 1;
       *out = l.release();
@@ -438,41 +527,101 @@ int pfscdc_index_read(pfscdc_ctx* ctx, const pfscdc_store* store, const void* ro
                       pfscdc_index_list** out) {
   if (!ctx || !store || !out) return PFSCDC_EINVAL;
   *out = nullptr;
-  pfscdc::ctx_index_stats(ctx) = pfscdc::IndexStats();
   std::unique_ptr<List> result(new List());
-  if (!root || !root_len) {  // r.topIdx == nil
-    *out = result.release();
+  if (int rc = read_index(ctx, store, root, root_len, IdxFilter(filter), &result, nullptr, nullptr))
+    return rc;
+  *out = result.release();
+  return PFSCDC_OK;
+}
+
+int pfscdc_index_read_dev(pfscdc_ctx* ctx, const pfscdc_store* store, const void* root,
+                          uint64_t root_len, const pfscdc_index_filter* filter,
+                          pfscdc_dev_list** out) {
+  if (!ctx || !store || !out) return PFSCDC_EINVAL;
+  *out = nullptr;
+  ResidentStats& rs = pfscdc::ctx_resident_stats(ctx);
+  rs.n[0] = rs.n[1] = 0;
+  const IdxFilter f(filter);
+  // no filter: every entry of a level is wanted, and the level of File entries is the result as
+  // the decode left it on the device
+  const bool whole = f.lower.empty() && f.upper.empty() && f.prefix.empty() && f.tag.empty();
+  std::unique_ptr<pfscdc_dev_list> keep;
+  if (whole && pfscdc::knob(pfscdc::Knob::IndexDecode) != 0) keep.reset(pfscdc::dev_list_new(ctx));
+  std::unique_ptr<List> result(new List());
+  bool kept = false;
+  if (int rc = read_index(ctx, store, root, root_len, f, &result, keep.get(), &kept)) return rc;
+  if (kept) {
+    rs.n[0] = 1;
+    *out = keep.release();
     return PFSCDC_OK;
   }
-  const IdxFilter f(filter);
-  // topLevel(): the root as a stream of one entry
-  std::unique_ptr<List> cur(new List());
-  {
-    const uint8_t *b = (const uint8_t*)root, *e = b + root_len;
-    IdxFrame fr;
-    if (!pfscdc::idx_parse(b, e, &fr, nullptr, 0) || !idx_append_frame(cur.get(), fr, b, e))
-      return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT, "the root index does not parse");
+  // the host path's list, uploaded
+  if (int rc = pfscdc::dev_list_upload(ctx, *result, out)) return rc;
+  rs.n[1] = sizeof(pfscdc_index_entry) * result->entries.size() +
+            sizeof(pfscdc_full_dataref) * result->drs.size() + result->blob.size();
+  return PFSCDC_OK;
+}
+
+int pfscdc_index_merge_dev(pfscdc_ctx* ctx, int mode, const pfscdc_dev_list* const* lists,
+                           uint32_t nfilesets, pfscdc_dev_list** out) {
+  if (!ctx || !out || (nfilesets && !lists) || nfilesets > (1u << 30) ||
+      (mode != PFSCDC_MERGE_FILES && mode != PFSCDC_MERGE_DELETIVE))
+    return PFSCDC_EINVAL;
+  *out = nullptr;
+  MergeStats& st = pfscdc::ctx_merge_stats(ctx);
+  st = MergeStats();
+  const uint32_t ns = mode == PFSCDC_MERGE_FILES ? 2 * nfilesets : nfilesets;
+  std::vector<MrgSrc> src(ns);
+  for (uint32_t k = 0; k < ns; k++) {
+    if (!lists[k]) continue;
+    if (lists[k]->device != pfscdc::ctx_device(ctx))
+      return pfscdc::ctx_fail(ctx, PFSCDC_EINVAL, "a resident list of another device");
+    src[k] = MrgSrc{lists[k]->entries, lists[k]->blob, lists[k]->drs,
+                    lists[k]->n, lists[k]->nb, lists[k]->nr};
   }
-  for (uint32_t level = 0;; level++) {
-    std::vector<uint32_t> sel, parents;
-    int64_t tail = -1;
-    const char* why = nullptr;
-    if (!select(*cur, f, &sel, &parents, &tail, &why))
-      return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT,
-                              "index level " + std::to_string(level) + " (its parent): " + why);
-    if (!sel.empty()) {
-      if (sel.size() == cur->entries.size() && result->entries.empty())
-        result.swap(cur);  // everything selected: the decoded list is the result
-      else
-        for (uint32_t i : sel) idx_append_entry(result.get(), *cur, cur->entries[i]);
-    }
-    if (parents.empty()) break;
-    if (level >= 64) return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT, "more than 64 index levels");
-    std::unique_ptr<List> next(new List());
-    if (int rc = read_level(ctx, store, level, *cur, parents, tail, next.get())) return rc;
-    cur.swap(next);
+  std::unique_ptr<pfscdc_dev_list> keep(pfscdc::dev_list_new(ctx));
+  bool ran = false;
+  if (int rc = merge_device(ctx, mode, src.data(), ns, hipMemcpyDeviceToDevice, nullptr, keep.get(), &ran))
+    return rc;
+  if (ran) {
+    st.n[0] = 1;
+    *out = keep.release();
+    return PFSCDC_OK;
   }
-  *out = result.release();
+  // the host arm: a stream out of order, or more than 2^32 - 1 records in
+  const float ms_rank = st.ms[1];
+  std::vector<std::unique_ptr<List>> own(ns);
+  std::vector<const List*> hl(ns, nullptr);
+  auto t0 = Clock::now();
+  for (uint32_t k = 0; k < ns; k++) {
+    if (!lists[k]) continue;
+    own[k].reset(new List());
+    if (int rc = pfscdc::dev_list_download(ctx, *lists[k], own[k].get())) return rc;
+    hl[k] = own[k].get();
+  }
+  const float ms_down = ms_since(t0);
+  t0 = Clock::now();
+  pfscdc_index_list* merged = nullptr;
+  int rc = mode == PFSCDC_MERGE_FILES ? pfscdc_index_merge(hl.data(), nfilesets, &merged)
+                                      : pfscdc_index_merge_deletive(hl.data(), nfilesets, &merged);
+  std::unique_ptr<List> m(merged);
+  if (rc) return pfscdc::ctx_fail(ctx, rc, "index merge: more than 2^32 - 1 records in the merged list");
+  const float ms_host = ms_since(t0);
+  t0 = Clock::now();
+  rc = pfscdc::dev_list_upload(ctx, *m, out);
+  const uint64_t n_in = st.n[1];
+  st = MergeStats();
+  st.n[1] = n_in;
+  st.n[3] = m->entries.size();
+  st.ms[0] = ms_since(t0);
+  st.ms[1] = ms_rank + ms_host;
+  st.ms[3] = ms_down;
+  return rc;
+}
+
+int pfscdc_last_resident_stats(pfscdc_ctx* ctx, uint64_t out[8]) {
+  if (!ctx || !out) return PFSCDC_EINVAL;
+  std::memcpy(out, pfscdc::ctx_resident_stats(ctx).n, sizeof(uint64_t) * 8);
   return PFSCDC_OK;
 }
 

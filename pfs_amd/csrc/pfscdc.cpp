@@ -14,6 +14,7 @@
 
 #include <unistd.h>
 
+#include "dev_list.h"
 #include "pfscdc_internal.h"
 
 using namespace pfscdc;
@@ -170,12 +171,14 @@ struct pfscdc_ctx {
   pfscdc_ctx* hash_after = nullptr;   // pfscdc_order_hash_after
   IndexStats index_stats;             // the last pfscdc_index_read
   MergeStats merge_stats;             // the last pfscdc_index_merge_ctx
+  ResidentStats resident_stats;       // the last calls over device-resident lists
 };
 
 namespace pfscdc {
 const pfscdc_params& ctx_params(const pfscdc_ctx* ctx) { return ctx->params; }
 IndexStats& ctx_index_stats(pfscdc_ctx* ctx) { return ctx->index_stats; }
 MergeStats& ctx_merge_stats(pfscdc_ctx* ctx) { return ctx->merge_stats; }
+ResidentStats& ctx_resident_stats(pfscdc_ctx* ctx) { return ctx->resident_stats; }
 int ctx_num_cus(const pfscdc_ctx* ctx) { return ctx->num_cus; }
 }  // namespace pfscdc
 
@@ -1622,7 +1625,74 @@ int hash_records_device(pfscdc_ctx* c, const uint8_t* data, uint64_t nbytes,
 // transform.go:50-53), with a compare against Ref.Id that leaves per-chunk ok flags on the
 // device; then the sliced ChaCha20 gather (chacha_slice_gather_kernel) over the non-empty
 // slices.  strict (pfscdc_store_read): the flags are fetched between the passes and a bad chunk
-// ends the call before the gather.
+// ends the call before the gather.  read_slices_impl stages the inputs; read_slices_run is
+// what both forms of the read path run from the verify pass on, once the chunks' offsets, Refs,
+// ok flags (c->d_offs, d_refs, d_rok from h_rok) and the nh hash records (c->d_segs, d_counts[1])
+// are enqueued: the hash pass and the id compare, strict mode's flags before the gather, the
+// gather over the m dense slices at d_slices / d_out_off / d_blk, the tar frame, the copy of a
+// host out.  named: the chunks a slice names (strict mode looks at those only).
+struct ReadRun {
+  const uint8_t* in;
+  uint64_t nbytes;
+  uint32_t nchunks, nh;
+  uint64_t longest, sum;
+  bool strict;
+  const uint8_t* named;
+  const pfscdc_slice* d_slices;
+  const uint64_t *d_out_off, *d_blk;
+  uint32_t m;
+  uint64_t nblocks;
+  uint8_t* outp;
+  void* out;
+  int out_on_device;
+  uint64_t out_bytes;
+  bool tar;
+  const TarEntry* d_tar;
+  const uint8_t* d_names;
+  uint32_t nent;
+  uint64_t begin, end, total;
+  uint8_t* chunk_ok;
+};
+
+static int read_slices_run(pfscdc_ctx* c, const ReadRun& r) {
+  hipStream_t st = c->stream;
+  const uint32_t nchunks = r.nchunks;
+  HIP_OK(c, hipEventRecord(c->rev[0], st));
+  HIP_OK(c, launch_blake2b(r.in, c->d_offs.p, c->d_segs.p, c->d_counts.p + 1, r.nh, c->d_order.p,
+                           c->d_qctr.p, c->num_cus, r.nbytes, st, false, nullptr,
+                           knob_waves(r.longest, r.sum, c->num_cus)));
+  HIP_OK(c, launch_verify_ids(c->d_segs.p, r.nh, c->d_refs.p, c->d_rok.p, st));
+  if (nchunks)
+    HIP_OK(c, hipMemcpyAsync(c->h_rok.p, c->d_rok.p, nchunks, hipMemcpyDeviceToHost, st));
+  HIP_OK(c, hipEventRecord(c->rev[1], st));
+  if (r.strict) {
+    HIP_OK(c, hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < nchunks; i++)
+      if (r.named[i] && !c->h_rok.p[i]) {
+        std::memcpy(r.chunk_ok, c->h_rok.p, nchunks);
+        return fail(c, PFSCDC_ECORRUPT, "a stored chunk failed verification");
+      }
+  }
+  HIP_OK(c, launch_slice_gather(r.in, c->d_offs.p, c->d_refs.p, c->d_rok.p, r.d_slices, r.d_out_off,
+                                r.d_blk, r.m, r.nblocks, r.outp, c->num_cus, st));
+  HIP_OK(c, hipEventRecord(c->rev[2], st));
+  if (r.tar) {
+    HIP_OK(c, launch_tar_frame(r.d_tar, r.d_names, r.nent, r.begin, r.end, r.total, r.outp,
+                               c->num_cus, st));
+    HIP_OK(c, hipEventRecord(c->rev[3], st));
+  }
+  if (!r.out_on_device && r.out_bytes)
+    HIP_OK(c, hipMemcpyAsync(r.out, r.outp, r.out_bytes, hipMemcpyDeviceToHost, st));
+  HIP_OK(c, hipStreamSynchronize(st));
+  if (nchunks) std::memcpy(r.chunk_ok, c->h_rok.p, nchunks);
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, c->rev[0], c->rev[1]) == hipSuccess) c->read_ms[0] = ms;
+  if (hipEventElapsedTime(&ms, c->rev[1], c->rev[2]) == hipSuccess) c->read_ms[1] = ms;
+  c->frame_ms = 0.f;
+  if (r.tar && hipEventElapsedTime(&ms, c->rev[2], c->rev[3]) == hipSuccess) c->frame_ms = ms;
+  return PFSCDC_OK;
+}
+
 int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctext_on_device,
                      const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
                      const uint8_t* verified, const pfscdc_slice* slices, uint32_t nslices,
@@ -1676,10 +1746,11 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
   HIP_OK(c, c->h_segs.ensure(nchunks));
   uint32_t nh = 0;
   uint64_t longest = 0, sum = 0;
+  std::vector<uint8_t> named(nchunks + 1, 0);
   for (uint32_t i = 0; i < nchunks; i++) {
-    const bool named = c->h_rok.p[i] == 0;
+    named[i] = c->h_rok.p[i] == 0;
     c->h_rok.p[i] = verified && verified[i] ? 1 : 0;
-    if (!named || c->h_rok.p[i]) continue;
+    if (!named[i] || c->h_rok.p[i]) continue;
     pfscdc_segment& sg = c->h_segs.p[nh++];
     std::memset(&sg, 0, sizeof sg);
     sg.size = chunk_offsets[i + 1] - chunk_offsets[i];
@@ -1729,8 +1800,6 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
   } else {
     HIP_OK(c, c->d_data.ensure(nbytes + 64));
     if (tar) {  // only the chunks the window's slices name, each run of them as one copy
-      std::vector<uint8_t> named(nchunks, 0);
-      for (uint32_t i = 0; i < nslices; i++) named[slices[i].chunk] = 1;
       for (uint32_t i = 0, j; i < nchunks; i = j) {
         for (j = i + 1; named[i] && j < nchunks && named[j];) j++;
         const uint64_t a = chunk_offsets[i], b = chunk_offsets[j];
@@ -1780,43 +1849,140 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
                              hipMemcpyHostToDevice, st));
   HIP_OK(c, hipMemcpyAsync(c->d_rmeta.p, c->h_rmeta.p, sizeof(uint64_t) * 2 * ((size_t)m + 1),
                            hipMemcpyHostToDevice, st));
-  HIP_OK(c, hipEventRecord(c->rev[0], st));
-  HIP_OK(c, launch_blake2b(in, c->d_offs.p, c->d_segs.p, c->d_counts.p + 1, nh, c->d_order.p,
-                           c->d_qctr.p, c->num_cus, nbytes, st, false, nullptr,
-                           knob_waves(longest, sum, c->num_cus)));
-  HIP_OK(c, launch_verify_ids(c->d_segs.p, nh, c->d_refs.p, c->d_rok.p, st));
-  if (nchunks)
-    HIP_OK(c, hipMemcpyAsync(c->h_rok.p, c->d_rok.p, nchunks, hipMemcpyDeviceToHost, st));
-  HIP_OK(c, hipEventRecord(c->rev[1], st));
-  if (strict) {
-    HIP_OK(c, hipStreamSynchronize(st));
-    for (uint32_t i = 0; i < nslices; i++)
-      if (!c->h_rok.p[slices[i].chunk]) {
-        std::memcpy(chunk_ok, c->h_rok.p, nchunks);
-        return fail(c, PFSCDC_ECORRUPT, "a stored chunk failed verification");
-      }
-  }
-  HIP_OK(c, launch_slice_gather(in, c->d_offs.p, c->d_refs.p, c->d_rok.p, c->d_rslices.p,
-                                c->d_rmeta.p, c->d_rmeta.p + m + 1, m, nblocks, outp,
-                                c->num_cus, st));
-  HIP_OK(c, hipEventRecord(c->rev[2], st));
-  if (tar) {
-    HIP_OK(c, launch_tar_frame(c->d_tar.p, c->d_tnames.p, nent, tar->begin, tar->end, tar->total,
-                               outp, c->num_cus, st));
-    HIP_OK(c, hipEventRecord(c->rev[3], st));
-  }
-  if (!out_on_device && out_bytes)
-    HIP_OK(c, hipMemcpyAsync(out, outp, out_bytes, hipMemcpyDeviceToHost, st));
-  HIP_OK(c, hipStreamSynchronize(st));
-  if (nchunks) std::memcpy(chunk_ok, c->h_rok.p, nchunks);
+  ReadRun run{};
+  run.in = in;
+  run.nbytes = nbytes;
+  run.nchunks = nchunks;
+  run.nh = nh;
+  run.longest = longest;
+  run.sum = sum;
+  run.strict = strict;
+  run.named = named.data();
+  run.d_slices = c->d_rslices.p;
+  run.d_out_off = c->d_rmeta.p;
+  run.d_blk = c->d_rmeta.p + m + 1;
+  run.m = m;
+  run.nblocks = nblocks;
+  run.outp = outp;
+  run.out = out;
+  run.out_on_device = out_on_device;
+  run.out_bytes = out_bytes;
+  run.tar = tar != nullptr;
+  run.d_tar = c->d_tar.p;
+  run.d_names = c->d_tnames.p;
+  run.nent = nent;
+  run.begin = tar ? tar->begin : 0;
+  run.end = tar ? tar->end : 0;
+  run.total = tar ? tar->total : 0;
+  run.chunk_ok = chunk_ok;
+  if (int rc = read_slices_run(c, run)) return rc;
   if (slice_ok)
     for (uint32_t i = 0; i < nslices; i++) slice_ok[i] = c->h_rok.p[slices[i].chunk];
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, c->rev[0], c->rev[1]) == hipSuccess) c->read_ms[0] = ms;
-  if (hipEventElapsedTime(&ms, c->rev[1], c->rev[2]) == hipSuccess) c->read_ms[1] = ms;
-  c->frame_ms = 0.f;
-  if (tar && hipEventElapsedTime(&ms, c->rev[2], c->rev[3]) == hipSuccess) c->frame_ms = ms;
   return PFSCDC_OK;
+}
+
+// read_slices_impl's sibling for a window planned on the device (pfscdc_dev_list_read_tar): the
+// dense slices, their places in out and their keystream block prefix lie on the device already
+// (the caller has held every slice against its chunk's stored length: launch_rtar_chunks), every
+// chunk of the batch is named by one of them, and the batch comes from host memory whole.
+// Strict, with the tar frame.  The bytes of every copy but the ciphertext's and the window's are
+// added to *h2d_bytes / *d2h_bytes where the copy is enqueued.
+int read_slices_dev_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes,
+                         const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
+                         const DevSlices& sl, void* out, int out_on_device, uint8_t* chunk_ok,
+                         const DevTar& tar, uint64_t* h2d_bytes, uint64_t* d2h_bytes) {
+  if (!c || !h2d_bytes || !d2h_bytes) return PFSCDC_EINVAL;
+  if (c->pending) return fail(c, PFSCDC_ESTATE, "read_slices during a pending scan");
+  if (!chunk_offsets || (nchunks && (!refs || !chunk_ok)) || (nbytes && !ctext))
+    return fail(c, PFSCDC_EINVAL, "NULL argument");
+  if (chunk_offsets[0] != 0 || chunk_offsets[nchunks] != nbytes)
+    return fail(c, PFSCDC_EINVAL, "chunk_offsets must start at 0 and end at nbytes");
+  const uint64_t out_bytes = tar.end - tar.begin;
+  if (out_bytes && !out) return fail(c, PFSCDC_EINVAL, "NULL argument");
+  c->scan_valid = false;
+  c->nsegs = 0;
+  c->have_refs = false;
+  HIP_OK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  for (auto& e : c->rev)
+    if (!e) HIP_OK(c, hipEventCreate(&e));
+  HIP_OK(c, c->h_rok.ensure(nchunks));
+  HIP_OK(c, c->h_segs.ensure(nchunks));
+  uint64_t longest = 0, sum = 0;
+  for (uint32_t i = 0; i < nchunks; i++) {
+    c->h_rok.p[i] = 0;
+    pfscdc_segment& sg = c->h_segs.p[i];
+    std::memset(&sg, 0, sizeof sg);
+    sg.size = chunk_offsets[i + 1] - chunk_offsets[i];
+    sg.file = i;
+    sg.flags = PFSCDC_SEG_VALID;
+    longest = std::max(longest, sg.size);
+    sum += sg.size;
+  }
+  HIP_OK(c, c->h_offs.ensure(nchunks + 1));
+  std::memcpy(c->h_offs.p, chunk_offsets, sizeof(uint64_t) * (nchunks + 1));
+  HIP_OK(c, c->h_refs.ensure(nchunks));
+  if (nchunks) std::memcpy(c->h_refs.p, refs, sizeof(pfscdc_ref) * nchunks);
+  HIP_OK(c, c->h_seg_begin.ensure(1));
+  c->h_seg_begin.p[0] = nchunks;
+  HIP_OK(c, c->d_offs.ensure(nchunks + 1));
+  HIP_OK(c, c->d_segs.ensure(nchunks));
+  HIP_OK(c, c->d_refs.ensure(nchunks));
+  HIP_OK(c, c->d_order.ensure(nchunks));
+  HIP_OK(c, c->d_qctr.ensure(2));
+  HIP_OK(c, c->d_counts.ensure(4));
+  HIP_OK(c, c->d_rok.ensure(nchunks));
+  HIP_OK(c, c->d_data.ensure(nbytes + 64));
+  if (nbytes) HIP_OK(c, hipMemcpyAsync(c->d_data.p, ctext, nbytes, hipMemcpyHostToDevice, st));
+  uint8_t* outp;
+  if (out_on_device) {
+    outp = (uint8_t*)out;
+  } else {
+    HIP_OK(c, c->d_out.ensure(out_bytes + 64));
+    outp = c->d_out.p;
+  }
+  HIP_OK(c, hipMemcpyAsync(c->d_offs.p, c->h_offs.p, sizeof(uint64_t) * (nchunks + 1),
+                           hipMemcpyHostToDevice, st));
+  *h2d_bytes += sizeof(uint64_t) * (nchunks + 1);
+  if (nchunks) {
+    HIP_OK(c, hipMemcpyAsync(c->d_refs.p, c->h_refs.p, sizeof(pfscdc_ref) * nchunks,
+                             hipMemcpyHostToDevice, st));
+    HIP_OK(c, hipMemcpyAsync(c->d_rok.p, c->h_rok.p, nchunks, hipMemcpyHostToDevice, st));
+    HIP_OK(c, hipMemcpyAsync(c->d_segs.p, c->h_segs.p, sizeof(pfscdc_segment) * nchunks,
+                             hipMemcpyHostToDevice, st));
+    *h2d_bytes += (sizeof(pfscdc_ref) + 1 + sizeof(pfscdc_segment)) * (uint64_t)nchunks;
+  }
+  HIP_OK(c, hipMemcpyAsync(c->d_counts.p + 1, c->h_seg_begin.p, sizeof(uint64_t),
+                           hipMemcpyHostToDevice, st));
+  *h2d_bytes += sizeof(uint64_t);
+  *d2h_bytes += nchunks;  // the ok flags read_slices_run fetches after the verify pass
+  const std::vector<uint8_t> named(nchunks + 1, 1);
+  ReadRun run{};
+  run.in = c->d_data.p;
+  run.nbytes = nbytes;
+  run.nchunks = run.nh = nchunks;
+  run.longest = longest;
+  run.sum = sum;
+  run.strict = true;
+  run.named = named.data();
+  run.d_slices = sl.slices;
+  run.d_out_off = sl.out_off;
+  run.d_blk = sl.blk_base;
+  run.m = sl.m;
+  run.nblocks = sl.nblocks;
+  run.outp = outp;
+  run.out = out;
+  run.out_on_device = out_on_device;
+  run.out_bytes = out_bytes;
+  run.tar = true;
+  run.d_tar = tar.entries;
+  run.d_names = tar.names;
+  run.nent = tar.nent;
+  run.begin = tar.begin;
+  run.end = tar.end;
+  run.total = tar.total;
+  run.chunk_ok = chunk_ok;
+  return read_slices_run(c, run);
 }
 
 // Split Ref.Id pass (ChaCha20 in parallel, then BLAKE2b of the ciphertext) when the chunk list

@@ -269,6 +269,29 @@ int read_slices_impl(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes, int ct
                      const uint8_t* verified, const pfscdc_slice* slices, uint32_t nslices,
                      void* out, int out_on_device, uint8_t* chunk_ok, uint8_t* slice_ok,
                      bool strict, const TarPlan* tar = nullptr);
+// The sibling for a window planned on the device (resident.cpp): m dense non-empty slices with
+// their places in out and the prefix of their keystream blocks (m + 1 entries each) as device
+// arrays, and the window's tar entries with the name table they point into.  The batch (host
+// ctext) holds exactly the chunks the slices name, and the caller has checked every slice against
+// its chunk's length (launch_rtar_chunks).  Strict; everything from the verify pass on is
+// read_slices_impl's.  *h2d_bytes / *d2h_bytes += the bytes of its copies other than the ciphertext
+// and the window.
+struct DevSlices {
+  const pfscdc_slice* slices;
+  const uint64_t *out_off, *blk_base;
+  uint32_t m;
+  uint64_t nblocks;
+};
+struct DevTar {
+  const TarEntry* entries;
+  const uint8_t* names;
+  uint32_t nent;
+  uint64_t begin, end, total;
+};
+int read_slices_dev_impl(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes,
+                         const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
+                         const DevSlices& sl, void* out, int out_on_device, uint8_t* chunk_ok,
+                         const DevTar& tar, uint64_t* h2d_bytes, uint64_t* d2h_bytes);
 // segs[i].file += base for i < n (a device group's gathered index: member-local file ids
 // become the commit's)
 hipError_t launch_rebase_files(pfscdc_segment* segs, uint64_t n, uint32_t base, hipStream_t st);
@@ -353,6 +376,84 @@ struct MergeStats {
   float ms[4] = {};
 };
 MergeStats& ctx_merge_stats(pfscdc_ctx* ctx);
+
+// ---- GetFileTAR over a device-resident list (resident.cpp; kernels in cdc_kernels.hip §10) ----
+struct RtarList {  // the three arrays of a pfscdc_dev_list
+  const pfscdc_index_entry* entries;
+  const char* blob;
+  const pfscdc_full_dataref* drs;
+  uint64_t n, nr, nb;  // entries, DataRefs, blob bytes (n, nr < 2^32)
+};
+// Sums of sizes saturate here: a sum that reaches it is past the 2^62 tar_plan refuses.
+constexpr uint64_t kRtarCap = (1ull << 62) + 1;
+// Why an entry has no place in the stream, in the order tar_plan finds them.
+enum RtarWhy : uint32_t {
+  kRtarBeyond = 1,  // pieces beyond the DataRef array
+  kRtarNotPacked,   // DataRefs not at [first, first + count) packed in entry order
+  kRtarString,      // path outside the blob
+  kRtarOverflow,    // the sizes' sum overflows
+  kRtarEmpty,       // tar_name_check's reasons
+  kRtarDirContent,
+  kRtarNotAscii,
+  kRtarTooBig,
+  kRtarNoSplit,
+  kRtarDirPieces,
+};
+constexpr unsigned long long kRtarNoErr = ~0ull;  // else entry index << 8 | RtarWhy
+struct RtarWindow {  // entries [i0, i1) meet the window; their DataRefs are [k0, k1)
+  uint64_t i0, i1, k0, k1;
+};
+struct RtarRun {  // a run of window pieces of one chunk
+  pfscdc_ref ref;
+  int64_t ref_size;
+  uint32_t first_piece, reserved;
+};
+static_assert(sizeof(RtarRun) == 80, "run record layout");
+// The runs' chunks as the batch read_slices_dev_impl takes (writer.cpp, beside StoreBatch):
+// table[r] = run r's chunk of the batch.  PFSCDC_ENOTFOUND: an id is not in the store;
+// PFSCDC_ECORRUPT: a stored chunk of another length than the run's ref_size.
+struct RunBatch {
+  std::vector<uint32_t> table;
+  std::vector<pfscdc_ref> refs;
+  std::vector<uint64_t> offs;
+  std::vector<uint8_t> ct;
+};
+int store_batch_runs(const pfscdc_store* s, const RtarRun* runs, uint32_t n, RunBatch* out);
+// flags[0] |= and flags[1] &= the flags of entries[0, n) (preset to 0 and ~0)
+hipError_t launch_index_flags(const pfscdc_index_entry* entries, uint64_t n, uint32_t* flags,
+                              int num_cus, hipStream_t st);
+// dsz[k] = DataRef k's size (saturated); *bad |= 1 for one StoreBatch::valid refuses (size 0)
+hipError_t launch_rtar_sizes(const pfscdc_full_dataref* drs, uint64_t nr, uint64_t* dsz,
+                             uint32_t* bad, int num_cus, hipStream_t st);
+// out[0, n] = saturating exclusive prefix sums of in[0, n); ent (nullable): ent[i].off = out[i]
+hipError_t launch_rtar_scan(const uint64_t* in, uint64_t n, uint64_t* out, TarEntry* ent,
+                            hipStream_t st);
+// per entry: the checks of tar_plan, ent[i] (off unset) and span[i] = 512 + roundup512(size)
+// (0 for a refused entry); *err = min(entry << 8 | RtarWhy) (preset to kRtarNoErr)
+hipError_t launch_rtar_entries(const RtarList& l, const uint64_t* dpre, TarEntry* ent,
+                               uint64_t* span, unsigned long long* err, int num_cus,
+                               hipStream_t st);
+// the entries that meet stream bytes [begin, end), by searches in off[0, n]
+hipError_t launch_rtar_window(const RtarList& l, const uint64_t* off, uint64_t begin, uint64_t end,
+                              RtarWindow* w, hipStream_t st);
+// Pieces of DataRefs [w.k0, w.k1) clipped to the window.  Count pass (slices == nullptr):
+// cnt[k - k0] = {non-empty, run head, keystream blocks}.  Fill pass, after launch_merge_scan of
+// cnt into base: the dense slices (chunk = the run's number), out_off, blk_base (m + 1) and runs.
+struct RtarPieces {
+  RtarList l;
+  const uint64_t* dpre;
+  const TarEntry* ent;
+  RtarWindow w;
+  uint64_t begin, end;
+};
+hipError_t launch_rtar_pieces(const RtarPieces& p, MrgCount* cnt, const uint64_t* base,
+                              pfscdc_slice* slices, uint64_t* out_off, uint64_t* blk_base,
+                              RtarRun* runs, int num_cus, hipStream_t st);
+// slices[j].chunk = table[slices[j].chunk] for j < m; *bad |= 1 (and chunk 0) for a slice that
+// does not lie inside its chunk of the batch (chunk_offs: nchunks + 1 offsets)
+hipError_t launch_rtar_chunks(pfscdc_slice* slices, uint64_t m, const uint32_t* table,
+                              const uint64_t* chunk_offs, uint32_t nchunks, uint32_t* bad, int num_cus,
+                              hipStream_t st);
 
 hipError_t launch_synth(uint8_t* out, const uint64_t* offs, uint32_t nfiles, const uint32_t* ids,
                         const uint64_t* starts, uint64_t seed, uint32_t mode, hipStream_t st);

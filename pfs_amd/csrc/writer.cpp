@@ -1111,6 +1111,27 @@ int pfscdc_store_read_tar(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_t
   return PFSCDC_OK;
 }
 
+// The batch of pfscdc_store_read_tar from the runs of a window planned on the device: the runs'
+// chunks in order of first use, deduplicated by id, and each run's chunk number.
+extern "C++" int pfscdc::store_batch_runs(const pfscdc_store* s, const pfscdc::RtarRun* runs, uint32_t n,
+                             pfscdc::RunBatch* out) {
+  StoreBatch b;
+  out->table.resize(n);
+  for (uint32_t r = 0; r < n; r++) {
+    pfscdc_full_dataref dr;
+    std::memset(&dr, 0, sizeof dr);
+    dr.ref = runs[r].ref;
+    dr.ref_size = runs[r].ref_size;
+    if (b.add(s, dr, &out->table[r])) return PFSCDC_ENOTFOUND;
+  }
+  if (b.corrupt) return PFSCDC_ECORRUPT;
+  b.concat();
+  out->refs.swap(b.refs);
+  out->offs.swap(b.offs);
+  out->ct.swap(b.ct);
+  return PFSCDC_OK;
+}
+
 int pfscdc_merge_file_hash(pfscdc_ctx* ctx, pfscdc_store* store, const pfscdc_full_dataref* drs,
                            uint32_t n, uint8_t out[32]) {
   if (!ctx || !store || !out || (n && !drs)) return PFSCDC_EINVAL;

@@ -390,6 +390,163 @@ def last_index_stats(chunker) -> dict:
     return out
 
 
+class DevIndexList:
+    """An owned pfscdc_dev_list: the three arrays of an index list on the GPU (what the decode
+    and merge kernels wrote, or an uploaded ``IndexList``); only the counts are on the host."""
+
+    def __init__(self, ptr, device: int):
+        self.lib = _lib.load()
+        self._p = ptr
+        self.device = device
+
+    def __len__(self) -> int:
+        return int(self.lib.pfscdc_dev_list_count(self._p))
+
+    @property
+    def num_datarefs(self) -> int:
+        return int(self.lib.pfscdc_dev_list_num_datarefs(self._p))
+
+    @property
+    def blob_len(self) -> int:
+        return int(self.lib.pfscdc_dev_list_blob_len(self._p))
+
+    @classmethod
+    def upload(cls, chunker, lst: Optional[IndexList]) -> "DevIndexList":
+        out = C.c_void_p()
+        rc = chunker.lib.pfscdc_dev_list_upload(chunker.ctx, lst._p if lst is not None else None,
+                                                C.byref(out))
+        if rc:
+            raise _lib.PfsCdcError(rc, "pfscdc_dev_list_upload")
+        return cls(out, chunker.device)
+
+    def download(self, chunker=None) -> IndexList:
+        """The list on the host, array for array."""
+        c = chunker if chunker is not None else Chunker(ChunkParams(), self.device)
+        try:
+            out = C.c_void_p()
+            rc = c.lib.pfscdc_dev_list_download(c.ctx, self._p, C.byref(out))
+        finally:
+            if chunker is None:
+                c.close()
+        if rc:
+            raise _lib.PfsCdcError(rc, "pfscdc_dev_list_download")
+        return IndexList(out)
+
+    def free(self) -> None:
+        if self._p:
+            self.lib.pfscdc_dev_list_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def index_read_dev(chunker, store, root: Optional[bytes], lower=None, upper=None, prefix=None,
+                   tag=None) -> DevIndexList:
+    """``index_read`` with a resident result (pfscdc_index_read_dev): with no filter the level-0
+    list stays on the device as the decode kernels wrote it."""
+    f = _filter(lower, upper, prefix, tag)
+    out = C.c_void_p()
+    rc = chunker.lib.pfscdc_index_read_dev(chunker.ctx, store._s, root, len(root) if root else 0,
+                                           C.byref(f) if f is not None else None, C.byref(out))
+    if rc:
+        msg = chunker.lib.pfscdc_last_error(chunker.ctx)
+        msg = msg.decode() if msg else ""
+        if rc == _lib.PFSCDC_ENOTFOUND:
+            raise KeyError(msg or "chunk not in the store")
+        raise _lib.PfsCdcError(rc, f"index read: {msg}")
+    return DevIndexList(out, chunker.device)
+
+
+def index_merge_dev(pairs, chunker, deletive: bool = False) -> DevIndexList:
+    """``index_merge`` over resident (deletive, additive) pairs with a resident result
+    (pfscdc_index_merge_dev); None stands for an empty list."""
+    pairs = list(pairs)
+    lists = [d for d, _ in pairs] if deletive else [x for d, a in pairs for x in (d, a)]
+    arr = (C.c_void_p * max(1, len(lists)))()
+    for i, l in enumerate(lists):
+        arr[i] = l._p if l is not None else None
+    out = C.c_void_p()
+    rc = chunker.lib.pfscdc_index_merge_dev(
+        chunker.ctx, _lib.MERGE_DELETIVE if deletive else _lib.MERGE_FILES, arr, len(pairs),
+        C.byref(out))
+    if rc:
+        msg = chunker.lib.pfscdc_last_error(chunker.ctx)
+        raise _lib.PfsCdcError(rc, f"index merge: {msg.decode() if msg else ''}")
+    return DevIndexList(out, chunker.device)
+
+
+def last_resident_stats(chunker) -> dict:
+    """Counts of the last resident calls on ``chunker``'s context
+    (pfscdc_last_resident_stats)."""
+    n = (C.c_uint64 * 8)()
+    chunker.lib.pfscdc_last_resident_stats(chunker.ctx, n)
+    return dict(zip(["read_resident", "read_uploaded_bytes", "runs", "chunks", "pieces",
+                     "d2h_bytes", "h2d_bytes", "plan_reused"], [int(x) for x in n]))
+
+
+class _DevTarStream(TarStream):
+    """TarStream over a resident list: layout and windows through pfscdc_dev_list_tar_layout
+    and pfscdc_dev_list_read_tar; nothing per file or per DataRef comes to the host."""
+
+    def __init__(self, storage, dev: DevIndexList):
+        self._dev = dev
+        self.device = storage.device
+        self._store = storage.store
+        self._offsets = None
+        self.last_stats = None
+        c = Chunker(ChunkParams(), self.device)
+        try:
+            total = C.c_uint64()
+            rc = c.lib.pfscdc_dev_list_tar_layout(c.ctx, dev._p, C.byref(total), None)
+            msg = c.lib.pfscdc_last_error(c.ctx)
+        finally:
+            c.close()
+        if rc:
+            raise _lib.PfsCdcError(rc, f"tar: {msg.decode('utf-8', 'replace') if msg else ''}")
+        self._total = total.value
+
+    @property
+    def entry_offsets(self) -> list:
+        if self._offsets is None:
+            c = Chunker(ChunkParams(), self.device)
+            try:
+                offs, total = (C.c_uint64 * (len(self._dev) + 1))(), C.c_uint64()
+                rc = c.lib.pfscdc_dev_list_tar_layout(c.ctx, self._dev._p, C.byref(total), offs)
+            finally:
+                c.close()
+            if rc:
+                raise _lib.PfsCdcError(rc, "pfscdc_dev_list_tar_layout")
+            self._offsets = list(offs)
+        return self._offsets
+
+    def _arrays(self):
+        if self._store is None:
+            raise ValueError("the storage has no chunk store to read from")
+        return None
+
+    def _read(self, ptr, cap: int, on_device: int, begin: int, n: int, chunker=None) -> int:
+        self._arrays()
+        c = chunker if chunker is not None else Chunker(ChunkParams(), self.device)
+        try:
+            nw = C.c_uint64()
+            rc = c.lib.pfscdc_dev_list_read_tar(c.ctx, self._store._s, self._dev._p, begin, n, ptr,
+                                                cap, on_device, C.byref(nw))
+            msg = c.lib.pfscdc_last_error(c.ctx)
+            self.last_stats = last_resident_stats(c)
+        finally:
+            if chunker is None:
+                c.close()
+        if rc == _lib.PFSCDC_ENOTFOUND:
+            raise KeyError("chunk not in the store")
+        if rc:
+            raise _lib.PfsCdcError(rc, f"TarStream: {msg.decode() if msg else ''}")
+        return nw.value
+
+
 class _FlatRefs:
     """The DataRefs of an IndexList as TarStream looks at them: their count, and their Ref
     ids when a missing chunk has to be named."""
@@ -438,8 +595,20 @@ class FileSet:
     """The merged view of opened filesets (``Storage.open``): the files that
     ``MergeReader.iterate`` yields, in path-then-tag order."""
 
-    def __init__(self, storage, merged: IndexList):
-        self._storage, self._list = storage, merged
+    def __init__(self, storage, merged: Optional[IndexList], resident: Optional[DevIndexList] = None):
+        self._storage, self._host, self._dev = storage, merged, resident
+
+    @property
+    def _list(self) -> IndexList:
+        """The merged list on the host (a resident fileset downloads it once, on first use)."""
+        if self._host is None:
+            self._host = self._dev.download()
+        return self._host
+
+    @property
+    def resident(self) -> Optional[DevIndexList]:
+        """The merged list on the device (``Storage.open(..., resident=True)``), else None."""
+        return self._dev
 
     def files(self) -> list:
         """``FileEntry`` (path, tag, size, DataRefs) per merged file."""
@@ -456,6 +625,8 @@ class FileSet:
 
     def tar(self) -> TarStream:
         """``GetFileTAR`` over the merged files (a ``TarStream``)."""
+        if self._dev is not None:
+            return _DevTarStream(self._storage, self._dev)
         return _ListTarStream(self._storage, self._list)
 
 
@@ -479,11 +650,15 @@ class Storage:
     def new_unordered_writer(self) -> "UnorderedWriter":
         return UnorderedWriter(self)
 
-    def open(self, filesets, lower=None, upper=None, prefix=None, tag=None) -> FileSet:
+    def open(self, filesets, lower=None, upper=None, prefix=None, tag=None,
+             resident: bool = False) -> FileSet:
         """The merged view of ``filesets`` (the ``Primitive`` infos ``UnorderedWriter.close()``
         returns, (additive root, deletive root) pairs, or bare additive roots), in order:
         both indexes of every fileset are read with the filter (index.Reader over the store)
-        and merged (MergeReader.iterate)."""
+        and merged (MergeReader.iterate).  ``resident``: the lists stay on the GPU from the
+        index read through the merge (pfscdc_index_read_dev, pfscdc_index_merge_dev) and
+        ``tar()`` renders from there; ``files()`` and ``read()`` download the merged list on
+        first use."""
         if self.store is None:
             raise ValueError("the storage has no chunk store to read from")
         roots = []
@@ -495,6 +670,18 @@ class Storage:
             else:
                 roots.append((fs.additive, fs.deletive))
         c = Chunker(ChunkParams(), self.device)
+        if resident:
+            try:
+                pairs = [(index_read_dev(c, self.store, d, lower, upper, prefix, tag),
+                          index_read_dev(c, self.store, a, lower, upper, prefix, tag))
+                         for a, d in roots]
+                merged = index_merge_dev(pairs, c)
+                for d, a in pairs:
+                    d.free()
+                    a.free()
+            finally:
+                c.close()
+            return FileSet(self, None, merged)
         try:
             pairs = [(index_read(c, self.store, d, lower, upper, prefix, tag),
                       index_read(c, self.store, a, lower, upper, prefix, tag))

@@ -43,7 +43,20 @@ profiles/r10/compact/merge.json.
 then the odd files again with every 16th file deleted), split into index reads, merges, copies
 (cheap-copied against re-rolled bytes) and close.  Writes profiles/r10/compact/compact.json.
 
-usage: python tools/read_bench.py [--tar | --index | --merge | --compact] [--chunks N]
+--resident: the two commits of --index opened and rendered as tar, the host hand-over
+(pfscdc_index_read of both roots, pfscdc_index_merge_ctx with PFSCDC_INDEX_MERGE=1,
+pfscdc_store_read_tar of the first 64 MiB window into a device tensor) against the same through
+the resident calls (pfscdc_index_read_dev, pfscdc_index_merge_dev, pfscdc_dev_list_read_tar),
+alternating call by call.  Per arm: median, min and max of each stage's and the whole call's wall
+time; the bytes each arm copies across the host link besides chunk ciphertext (the resident
+arm's tar figures are the library's tallies of its copies; the host arm's are computed from the
+lists' array sizes and from what pfscdc_store_read_tar uploads per piece, entry and chunk); the
+window's runs.
+Every resident window is compared with the host hand-over's bytes.  Writes
+profiles/r11/resident/resident.json.
+
+usage: python tools/read_bench.py [--tar | --index | --merge | --compact | --resident]
+                                  [--chunks N]
                                   [--chunk-bytes B] [--files N] [--reps R] [--warmup W]
                                   [--out PATH]"""
 import argparse
@@ -243,6 +256,131 @@ def index_rows(args):
     return rows
 
 
+def resident_rows(args):
+    """--resident: the two commits of --index opened and rendered, host hand-over against the
+    resident calls, alternating call by call."""
+    import ctypes as C
+    import time
+
+    from pfs_amd import chunk as pc
+    from pfs_amd import fileset as PF
+    window = 64 << 20
+    rows = []
+    for nfiles, fbytes in ((65536, 4096), (1 << 20, 256)):
+        store = pc.ChunkStore()
+        st = PF.Storage(0, ChunkParams(), store=store)
+        w = st.new_unordered_writer()
+        data = np.random.default_rng(nfiles).integers(0, 256, nfiles * fbytes + 64, dtype=np.uint8)
+        for i in range(nfiles):
+            w.put("/bench/d%03d/f%07d" % (i >> 12, i), "", False, data[i * fbytes:(i + 1) * fbytes])
+        infos = w.close()
+        w.release()
+        assert len(infos) == 1
+        roots = (infos[0].deletive, infos[0].additive)
+        c = Chunker(ChunkParams(), 0)
+        lib = c.lib
+        out_a = torch.empty(window, dtype=torch.uint8, device="cuda:0")
+        out_b = torch.empty(window, dtype=torch.uint8, device="cuda:0")
+        _lib.set_knob("PFSCDC_INDEX_MERGE", 1)
+        runs = {"a": [], "b": []}
+        traffic = {}
+
+        def list_bytes(n, ndr, blob):
+            return 64 * n + 128 * ndr + blob
+
+        for i in range(args.warmup + args.reps):
+            # (a) the host hand-over
+            out_a.fill_(0xA5)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lists = [PF.index_read(c, store, r) for r in roots]
+            t1 = time.perf_counter()
+            merged = PF.index_merge([tuple(lists)], chunker=c)
+            t2 = time.perf_counter()
+            n, ents, blob, drs, ndr = merged._views()
+            tf = lib.pfscdc_index_list_tar_files(merged._p)
+            nw = C.c_uint64()
+            rc = lib.pfscdc_store_read_tar(c.ctx, store._s, tf, n, drs, ndr, 0, window,
+                                           out_a.data_ptr(), window, 1, C.byref(nw))
+            t3 = time.perf_counter()
+            if rc:
+                raise SystemExit(f"read_bench: pfscdc_store_read_tar: {rc}")
+            got_a = nw.value
+            runs["a"].append({"read_ms": (t1 - t0) * 1e3, "merge_ms": (t2 - t1) * 1e3,
+                              "tar_ms": (t3 - t2) * 1e3, "wall_ms": (t3 - t0) * 1e3})
+            if i == 0:
+                sizes = [(len(x), x._views()[4], len(x._views()[2])) for x in lists]
+                ins = sum(list_bytes(*s) for s in sizes)
+                traffic["a_read_d2h"] = ins
+                traffic["a_merge_h2d"] = ins
+                traffic["a_merge_d2h"] = list_bytes(n, ndr, len(blob))
+            for x in lists:
+                x.free()
+            # (b) the resident calls
+            out_b.fill_(0xA5)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dl = [PF.index_read_dev(c, store, r) for r in roots]
+            up_bytes = PF.last_resident_stats(c)["read_uploaded_bytes"]
+            t1 = time.perf_counter()
+            dm = PF.index_merge_dev([tuple(dl)], c)
+            t2 = time.perf_counter()
+            rc = lib.pfscdc_dev_list_read_tar(c.ctx, store._s, dm._p, 0, window, out_b.data_ptr(),
+                                              window, 1, C.byref(nw))
+            t3 = time.perf_counter()
+            if rc:
+                raise SystemExit(f"read_bench: pfscdc_dev_list_read_tar: {rc}")
+            rs = PF.last_resident_stats(c)
+            if nw.value != got_a or not torch.equal(out_a, out_b):
+                raise SystemExit("read_bench: the resident window differs from the host hand-over's")
+            runs["b"].append({"read_ms": (t1 - t0) * 1e3, "merge_ms": (t2 - t1) * 1e3,
+                              "tar_ms": (t3 - t2) * 1e3, "wall_ms": (t3 - t0) * 1e3})
+            if i == 0:
+                # computed, not measured: what (a)'s pfscdc_store_read_tar uploads for the same
+                # window besides ciphertext:
+                # 24 B per piece, two 8 B prefixes per piece (+1), 24 B and the name per entry,
+                # and per chunk its offset, Ref, ok flag and hash record
+                e = np.frombuffer(C.string_at(ents, 64 * n), dtype=np.uint8).reshape(n, 64)
+                plen = e[:, 24:28].copy().view(np.uint32).ravel()
+                offs, total = (C.c_uint64 * (n + 1))(), C.c_uint64()
+                lib.pfscdc_dev_list_tar_layout(c.ctx, dm._p, C.byref(total), offs)
+                nent = int(np.searchsorted(np.frombuffer(offs, dtype=np.uint64), window))
+                per_chunk = 8 + 64 + 1 + 56
+                traffic["a_tar_h2d"] = 24 * rs["pieces"] + 16 * (rs["pieces"] + 1) + 24 * nent + \
+                    int(plen[:nent].sum()) + per_chunk * rs["chunks"] + 16
+                traffic["a_tar_d2h"] = rs["chunks"]
+                traffic["b_read_h2d"] = up_bytes
+                traffic["b_tar_d2h"] = rs["d2h_bytes"]
+                traffic["b_tar_h2d"] = rs["h2d_bytes"]
+                traffic["window_entries"] = nent
+                traffic["window_pieces"] = rs["pieces"]
+                traffic["window_runs"] = rs["runs"]
+                traffic["window_chunks"] = rs["chunks"]
+                traffic["window_bytes"] = got_a
+            merged.free()
+            for x in dl + [dm]:
+                x.free()
+        _lib.set_knob("PFSCDC_INDEX_MERGE", 0)
+        c.close()
+        row = {"files": nfiles, "file_bytes": fbytes, "reps": args.reps, "warmup": args.warmup,
+               "windows_equal": True, "traffic_bytes_excluding_ciphertext": traffic}
+        for arm, name in (("a", "host_handover"), ("b", "resident")):
+            r = runs[arm][args.warmup:]
+            row[name] = {k: {"median": round(statistics.median(x[k] for x in r), 3),
+                             "min": round(min(x[k] for x in r), 3),
+                             "max": round(max(x[k] for x in r), 3)}
+                         for k in ("read_ms", "merge_ms", "tar_ms", "wall_ms")}
+        a, b = row["host_handover"]["wall_ms"], row["resident"]["wall_ms"]
+        row["margin_ms"] = round(a["median"] - b["median"], 3)
+        row["spread_ms"] = {"host_handover": round(a["max"] - a["min"], 3),
+                            "resident": round(b["max"] - b["min"], 3)}
+        row["resident_wins_by_more_than_both_spreads"] = bool(
+            row["margin_ms"] > max(row["spread_ms"].values()))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def synthetic_lists(ids, seed):
     """The deletive and additive index lists of one fileset whose files are /bench/dDDD/fNNNNNNN
     for N in ids (ascending), each Put without append (so every file has a deletive entry too)
@@ -428,6 +566,7 @@ def main():
     ap.add_argument("--index", action="store_true")
     ap.add_argument("--merge", action="store_true")
     ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--resident", action="store_true")
     ap.add_argument("--files", type=int, default=1 << 20)
     ap.add_argument("--tar", action="store_true")
     ap.add_argument("--chunks", type=int, default=1024)
@@ -449,6 +588,16 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/read_bench.py --" + what,
+                       "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
+            f.write("\n")
+        return
+    if args.resident:
+        if args.out == os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json"):
+            args.out = os.path.join(ROOT, "profiles", "r11", "resident", "resident.json")
+        rows = resident_rows(args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/read_bench.py --resident",
                        "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
             f.write("\n")
         return
