@@ -889,6 +889,98 @@ int pfscdc_dev_list_read_tar(pfscdc_ctx* ctx, const pfscdc_store* store, pfscdc_
  * bytes copied host to device except chunk ciphertext, out[7] 1 the cached plan was reused. */
 int pfscdc_last_resident_stats(pfscdc_ctx* ctx, uint64_t out[8]);
 
+/* ---- the Source: directory entries, path filters and FileInfo (src/server/pfs/server/
+ * source.go:28-157, driver_file.go:173-385; fileset/dir_inserter.go:22-58, transforms.go:31-49) ----
+ * Every PFS file RPC wraps the opened commit in a Source.  The input is a level-0 list in
+ * (path, tag) order (what pfscdc_index_read[_dev] or pfscdc_index_merge[_dev] returns; the open
+ * has applied index.WithPrefix and WithTag).  The result:
+ *   1. dirInserter: a directory entry Index{Path: dir, File: {}} (empty tag, no DataRefs, size 0)
+ *      in front of the first entry under every directory, "/" included;
+ *   2. indexFilter: the entries a path predicate selects (below), directories included;
+ *   3. source.Iterate: per selected entry a pfscdc_file_info.  A file: its size_bytes and
+ *      hashDataRefs (fileset/util.go:149-158: BLAKE2b-256 over its DataRefs' hashes; the hash of
+ *      the empty string for none), or the caller's leaf hash.  A directory: the wrapping sum of
+ *      its descendants' file sizes and BLAKE2b-256 over its immediate children's hashes in stream
+ *      order (sub-directories and each tag of one path count as a child).
+ * The result's list holds the selected entries with a fresh blob and the compacted DataRefs of the
+ * selected entries, first packed in entry order, so the tar calls take it as it is and write one
+ * entry per entry of the stream, directories (typeflag 5) included: GetFileTAR as served.
+ * Predicates (arg goes through cleanPath here; "" and "/" name the root):
+ *   PFSCDC_SRC_ALL      everything (arg ignored);
+ *   PFSCDC_SRC_SUBTREE  inspectFile / walkFile / diffFile: path == p || HasPrefix(path, p + "/"),
+ *                       p = cleanPath(arg), "" for the root;
+ *   PFSCDC_SRC_LIST     listFile: not Clean(name, true) itself, else path == name or
+ *                       HasPrefix(path, Clean(name, true)); PFSCDC_INFO_CHILD is set in the flags
+ *                       of the entries with pathIsChild(name, cleanPath(path));
+ *   PFSCDC_SRC_GET      getFile's `full` filter for a literal glob: path == glob, path == glob + "/"
+ *                       or HasPrefix(path, glob + "/"); "/" selects everything.  A glob holding one
+ *                       of *?[]{}!()@+^ or a backslash: PFSCDC_EUNSUPPORTED with the glob named.
+ * PFSCDC_ENOTFOUND (NewErrOnEmpty): nothing selected by GET, or by SUBTREE with p != "".
+ * PFSCDC_EINVAL: an entry with a Range (not a level-0 list), or strings / DataRefs outside the
+ * list's arrays. */
+#define PFSCDC_SRC_ALL 0
+#define PFSCDC_SRC_SUBTREE 1
+#define PFSCDC_SRC_LIST 2
+#define PFSCDC_SRC_GET 3
+#define PFSCDC_FILE_TYPE_FILE 1u /* pfs.FileType_FILE */
+#define PFSCDC_FILE_TYPE_DIR 2u  /* pfs.FileType_DIR: the path ends in '/' */
+#define PFSCDC_INFO_CHILD 1u
+typedef struct pfscdc_file_info {
+  uint8_t hash[32];
+  int64_t size;
+  uint32_t type;  /* PFSCDC_FILE_TYPE_* */
+  uint32_t flags; /* PFSCDC_INFO_* */
+} pfscdc_file_info; /* 48 bytes */
+
+/* The Source on the host, with no GPU call: emit() of dirInserter.Iterate, indexFilter.Iterate
+ * with its dir state and source.Iterate's recursion over a second iterator with its cache, taken
+ * literally.  The specification of pfscdc_source_open, and its arm for the lists the device
+ * refuses.  leaf_hashes (nullable): 32 bytes per entry of in, used as the files' hashes (the
+ * reference's MergeFileReader.Hash when more than one fileset was opened, storage.go:124-127).
+ * *out: pfscdc_index_list_free; *infos (one per entry of *out): pfscdc_file_infos_free.  On an
+ * error both are NULL and pfscdc_source_host_error names it (per thread, until the next call). */
+int pfscdc_source_host(const pfscdc_index_list* in, int kind, const char* arg,
+                       const uint8_t* leaf_hashes, pfscdc_index_list** out,
+                       pfscdc_file_info** infos);
+const char* pfscdc_source_host_error(void);
+void pfscdc_file_infos_free(pfscdc_file_info* infos);
+
+/* The Source over a resident list on ctx.  The PFSCDC_SOURCE knob: 1 runs the device arm
+ * (per input entry the new ancestors by the common prefix with its predecessor and the predicate on
+ * each, prefix sums, a fill at the item's own ranges and the DataRef copy; per output entry its depth
+ * and its subtree's end by a search, directory sizes as differences of one prefix sum; the leaf
+ * hashes in one BLAKE2b launch and then one launch per depth, deepest first, over the children's
+ * hashes gathered 32 bytes apart), 0 downloads the list, calls pfscdc_source_host and uploads its
+ * result; list and infos are identical.  The device arm hands a call to the host arm for a list
+ * that is not in (path, tag) order, that holds a path not IsClean(p, IsDir(p)), or that holds one
+ * directory path twice; pfscdc_last_source_stats says which ran.  leaf_hashes as
+ * pfscdc_source_host's, on the device when leaf_on_device.  Errors and their texts
+ * (pfscdc_last_error) as pfscdc_source_host's, with *out NULL.  Every array the kernels fill ends
+ * in a 64-byte guard that the call checks (PFSCDC_EHIP). */
+typedef struct pfscdc_source pfscdc_source;
+int pfscdc_source_open(pfscdc_ctx* ctx, const pfscdc_dev_list* in, int kind, const char* arg,
+                       const uint8_t* leaf_hashes, int leaf_on_device, pfscdc_source** out);
+/* The same over a host list, which is uploaded first (NULL: an empty list). */
+int pfscdc_source_open_list(pfscdc_ctx* ctx, const pfscdc_index_list* in, int kind,
+                            const char* arg, const uint8_t* leaf_hashes, int leaf_on_device,
+                            pfscdc_source** out);
+/* The result's list, owned by the source: pfscdc_dev_list_read_tar, _tar_layout and _download
+ * take it as it is. */
+pfscdc_dev_list* pfscdc_source_list(pfscdc_source* s);
+uint32_t pfscdc_source_count(const pfscdc_source* s);
+/* The infos copied to out (pfscdc_source_count records). */
+int pfscdc_source_infos(pfscdc_ctx* ctx, const pfscdc_source* s, pfscdc_file_info* out);
+int pfscdc_source_free(pfscdc_source* s);
+/* The last pfscdc_source_open on ctx: out[0] 1 the device arm ran, 0 the host arm; out[1] entries
+ * in; out[2] entries out; out[3] directories inserted and selected; out[4] levels (the deepest
+ * entry's depth); out[5] BLAKE2b launches; out[6] bytes copied host to device; out[7] bytes copied
+ * device to host (pfscdc_source_infos not counted). */
+int pfscdc_last_source_stats(pfscdc_ctx* ctx, uint64_t out[8]);
+/* Its time (ms, wall time around synchronised stages): out[0] insert and select (count, prefix
+ * sums, fill, DataRef copy; host arm: the download, the host call and the upload), out[1] depths,
+ * subtree ends and sizes, out[2] the leaf hashes, out[3] the directory levels. */
+int pfscdc_last_source_timings(pfscdc_ctx* ctx, float out[4]);
+
 /* shard (fileset/shard.go:27-49) over a merged list: cb receives each shard's path range
  * (lower, upper; "" = an open end).  A range is closed in front of the first file that finds
  * threshold or more content bytes collected (the test comes before the file is added); its upper

@@ -78,6 +78,10 @@ EXPORTED = [
     "pfscdc_dev_list_num_datarefs", "pfscdc_dev_list_blob_len", "pfscdc_dev_list_free",
     "pfscdc_index_read_dev", "pfscdc_index_merge_dev", "pfscdc_dev_list_tar_layout",
     "pfscdc_dev_list_read_tar", "pfscdc_last_resident_stats",
+    "pfscdc_source_host", "pfscdc_source_host_error", "pfscdc_file_infos_free",
+    "pfscdc_source_open", "pfscdc_source_open_list", "pfscdc_source_list", "pfscdc_source_count",
+    "pfscdc_source_infos", "pfscdc_source_free", "pfscdc_last_source_stats",
+    "pfscdc_last_source_timings",
 ]
 
 
@@ -141,6 +145,16 @@ class IndexEntry(C.Structure):
 IDX_HAS_RANGE, IDX_HAS_FILE, IDX_HAS_CHUNK_REF = 1, 2, 4
 
 
+class FileInfoC(C.Structure):
+    _fields_ = [("hash", C.c_uint8 * 32), ("size", C.c_int64), ("type", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+SRC_ALL, SRC_SUBTREE, SRC_LIST, SRC_GET = 0, 1, 2, 3
+FILE_TYPE_FILE, FILE_TYPE_DIR = 1, 2
+INFO_CHILD = 1
+
+
 class AnnotationOut(C.Structure):
     _fields_ = [("user", C.c_uint64), ("has_data_ref", C.c_int32), ("reserved", C.c_int32),
                 ("data_ref", DataRef)]
@@ -164,7 +178,7 @@ MERGE_FILES, MERGE_DELETIVE = 0, 1
 SHARD_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_char_p)
 UW_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(UwEvent))
 
-assert C.sizeof(IndexEntry) == 64
+assert C.sizeof(IndexEntry) == 64 and C.sizeof(FileInfoC) == 48
 assert C.sizeof(Segment) == 56 and C.sizeof(Params) == 32 and C.sizeof(ChunkRef) == 96 and C.sizeof(FullDataRef) == 128
 
 WRITER_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(ChunkRef), C.POINTER(AnnotationOut),
@@ -375,6 +389,17 @@ def load() -> C.CDLL:
             "pfscdc_dev_list_tar_layout": (i32, [vp, vp, P(u64), P(u64)]),
             "pfscdc_dev_list_read_tar": (i32, [vp, vp, vp, u64, u64, vp, u64, i32, P(u64)]),
             "pfscdc_last_resident_stats": (i32, [vp, P(u64)]),
+            "pfscdc_source_host": (i32, [vp, i32, C.c_char_p, vp, P(vp), P(P(FileInfoC))]),
+            "pfscdc_source_host_error": (C.c_char_p, []),
+            "pfscdc_file_infos_free": (None, [P(FileInfoC)]),
+            "pfscdc_source_open": (i32, [vp, vp, i32, C.c_char_p, vp, i32, P(vp)]),
+            "pfscdc_source_open_list": (i32, [vp, vp, i32, C.c_char_p, vp, i32, P(vp)]),
+            "pfscdc_source_list": (vp, [vp]),
+            "pfscdc_source_count": (u32, [vp]),
+            "pfscdc_source_infos": (i32, [vp, vp, P(FileInfoC)]),
+            "pfscdc_source_free": (i32, [vp]),
+            "pfscdc_last_source_stats": (i32, [vp, P(u64)]),
+            "pfscdc_last_source_timings": (i32, [vp, P(C.c_float)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

@@ -3355,4 +3355,393 @@ hipError_t launch_rtar_chunks(pfscdc_slice* slices, uint64_t m, const uint32_t* 
   return hipGetLastError();
 }
 
+// ---- 11. The Source: directory entries, path filters and FileInfo ------------------------------
+// (fileset/dir_inserter.go:22-58 emit / parentOf, fileset/transforms.go:31-49 indexFilter,
+// server/pfs/server/source.go:45-145 Iterate / computeFileInfo; source.cpp takes them literally)
+//
+// Directory insertion without the running lastPath.  emit(p) inserts parent = Clean(parentOf(p),
+// true) exactly when lastPath < parent, recursively, so the directories put in front of p are its
+// ancestors a (every prefix p[0..k] with p[k] == '/', k < len - 1: the entry itself is not its own
+// ancestor) with lastPath < a, lastPath being the entry emitted before.  Claim: for a list of
+// clean paths in ascending order, with q the input entry before p, lastPath < a <=> a is not a
+// prefix of q <=> k >= lcp(q, p).  Proof: (1) if a is a prefix of q, then q >= a, and every entry
+// emitted since q (q's own and then p's shorter ancestors, each a prefix of p, emitted in
+// ascending length) is >= a too or is a itself already emitted; in either case lastPath >= a.
+// (2) if a is not a prefix of q: q <= p and a is a prefix of p.  Were q >= a, then a <= q <= p
+// with a a prefix of p but not of q; at the first byte where q and a differ (q is no proper
+// prefix of a, else q < a) q holds the larger byte, so q > every string with prefix a, p
+// included: contradiction.  So q < a; the ancestors of p emitted after q and before a are proper
+// prefixes of a, hence < a.  So lastPath < a.  (3) a is a prefix of q iff its k + 1
+// bytes lie inside the common prefix, k < lcp.  For the first entry lastPath = "" < every
+// ancestor: lcp = 0.  The same argument shows that the output is ascending, so a directory's
+// subtree (the paths with its prefix) lies contiguously after it, and since each of the four
+// predicates selects a selected directory's subtree whole, computeFileInfo's recursion over the
+// second iterator with its cache reduces to: a directory's children are the entries of the next
+// depth inside its subtree, in order (tests/source_oracle.py holds both against the literal
+// forms).
+// 11a count  one lane per input entry: order and cleanliness against its predecessor (flags for
+//     the host arm), lcp, the new ancestors and the entry itself under the predicate:
+//     {entries, DataRefs, blob bytes} it emits.
+// 11b scan   merge_scan_kernel as it is.
+// 11c fill   one lane per input entry writes its directories and itself at its own ranges
+//     (nothing unless its counts equal them), one MrgCopy per selected file for
+//     merge_copy_kernel, and per output entry {source, depth}, type, flags and its file size.
+// 11d tree   one lane per output entry: a directory's subtree end by a search for the first path
+//     without its prefix; its size a difference of the prefix sums of the file sizes (wrapping).
+// 11e leaf   the files' DataRef hashes packed 32 bytes apart, one segment per entry, for one
+//     blake2b_kernel launch (or the caller's leaf hashes copied in).
+// 11f level  per depth L, deepest first: {entry of depth L + 1, directory of depth L} counted and
+//     prefix-summed (merge_scan_kernel); the children's hashes gathered at 32 x their number
+//     among the entries of depth L + 1 (every such entry between a directory and its subtree's
+//     end is its child), one segment per directory; one blake2b_kernel launch; the digests
+//     scattered into the infos, where level L - 1 reads them.
+PFS_DEV bool src_selected(const SrcPred& p, const uint8_t* s, uint32_t n) {
+  if (p.all) return true;
+  bool eq = n == p.name_len, pre = n >= p.dir_len;
+  for (uint32_t k = 0; eq && k < n; k++) eq = s[k] == (uint8_t)p.name[k];
+  for (uint32_t k = 0; pre && k < p.dir_len; k++) pre = s[k] == (uint8_t)p.dir[k];
+  if (!eq && !pre) return false;
+  return !(p.exclude_dir && pre && n == p.dir_len);
+}
+
+// pathIsChild(name, cleanPath(path)) for a clean path (paths.go:39-46)
+PFS_DEV uint32_t src_child(const SrcPred& p, const uint8_t* s, uint32_t n) {
+  if (!p.child_flag) return 0;
+  const uint32_t cn = (n > 1 && s[n - 1] == '/') ? n - 1 : n;
+  if (cn < p.name_len) return 0;
+  for (uint32_t k = 0; k < p.name_len; k++)
+    if (s[k] != (uint8_t)p.name[k]) return 0;
+  uint32_t a = p.name_len, b = cn;
+  while (a < b && s[a] == '/') a++;
+  while (b > a && s[b - 1] == '/') b--;
+  for (uint32_t k = a; k < b; k++)
+    if (s[k] == '/') return 0;
+  return PFSCDC_INFO_CHILD;
+}
+
+PFS_DEV bool src_entry_ok(const RtarList& in, const pfscdc_index_entry& e) {
+  return e.path_off <= in.nb && e.path_len <= in.nb - e.path_off && e.tag_off <= in.nb &&
+         e.tag_len <= in.nb - e.tag_off && e.last_path_off <= in.nb &&
+         e.last_path_len <= in.nb - e.last_path_off && e.first <= in.nr &&
+         e.count <= in.nr - e.first;
+}
+
+// What input entry i emits, *lcp its common prefix with the entry before, *bad |= SrcBad.
+PFS_DEV MrgCount src_item(const RtarList& in, const SrcPred& pr, uint64_t i, uint32_t* bad,
+                          uint32_t* lcp) {
+  MrgCount c{0, 0, 0};
+  *lcp = 0;
+  const pfscdc_index_entry e = in.entries[i];
+  if (!src_entry_ok(in, e)) {
+    *bad |= kSrcMalformed;
+    return c;
+  }
+  if (e.flags & (PFSCDC_IDX_HAS_RANGE | PFSCDC_IDX_HAS_CHUNK_REF)) *bad |= kSrcNotLevel0;
+  const uint8_t* s = (const uint8_t*)in.blob + e.path_off;
+  const uint32_t n = e.path_len;
+  // IsClean(p, IsDir(p)): rooted, no empty component but a last one, none of "." or ".."
+  bool clean = n > 0 && s[0] == '/';
+  for (uint32_t k = 1, start = 1; clean && k <= n; k++) {
+    if (k < n && s[k] != '/') continue;
+    const uint32_t cl = k - start;
+    if (cl == 0) clean = k == n;
+    else if (cl == 1) clean = s[start] != '.';
+    else if (cl == 2) clean = s[start] != '.' || s[start + 1] != '.';
+    start = k + 1;
+  }
+  if (!clean) *bad |= kSrcUnclean;
+  uint32_t l = 0;
+  if (i > 0) {
+    const pfscdc_index_entry q = in.entries[i - 1];
+    if (!src_entry_ok(in, q)) {
+      *bad |= kSrcMalformed;
+      return c;
+    }
+    const uint8_t* t = (const uint8_t*)in.blob + q.path_off;
+    const uint32_t m = n < q.path_len ? n : q.path_len;
+    while (l < m && s[l] == t[l]) l++;
+    int cmp = l < m ? (t[l] < s[l] ? -1 : 1) : q.path_len < n ? -1 : q.path_len > n ? 1 : 0;
+    if (cmp == 0) {
+      if (n && s[n - 1] == '/') *bad |= kSrcDirTwice;
+      cmp = mrg_cmp_str((const uint8_t*)in.blob + q.tag_off, q.tag_len,
+                        (const uint8_t*)in.blob + e.tag_off, e.tag_len);
+    }
+    if (cmp > 0) *bad |= kSrcUnordered;
+  }
+  *lcp = l;
+  for (uint32_t k = l; k + 1 < n; k++)
+    if (s[k] == '/' && src_selected(pr, s, k + 1)) {
+      c.emit++;
+      c.blob += (uint64_t)k + 4;  // the path and three NULs (path, empty tag, empty LastPath)
+    }
+  if (src_selected(pr, s, n)) {
+    c.emit++;
+    c.recs = e.count;
+    c.blob += (uint64_t)n + e.tag_len + e.last_path_len + 3;
+  }
+  return c;
+}
+
+__global__ __launch_bounds__(kIdxBlock) void src_count_kernel(RtarList in, SrcPred pr,
+                                                              MrgCount* __restrict__ cnt,
+                                                              uint32_t* __restrict__ bad) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; i < in.n;
+       i += (uint64_t)gridDim.x * kIdxBlock) {
+    uint32_t b = 0, lcp;
+    cnt[i] = src_item(in, pr, i, &b, &lcp);
+    if (b) atomicOr(bad, b);
+  }
+}
+
+__global__ __launch_bounds__(kIdxBlock) void src_fill_kernel(
+    RtarList in, SrcPred pr, const MrgCount* __restrict__ cnt, const uint64_t* __restrict__ base,
+    pfscdc_index_entry* __restrict__ entries, char* __restrict__ blob, MrgCopy* __restrict__ copy,
+    SrcMeta* __restrict__ meta, pfscdc_file_info* __restrict__ infos, MrgCount* __restrict__ sizes,
+    uint32_t* __restrict__ maxdepth) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; i < in.n;
+       i += (uint64_t)gridDim.x * kIdxBlock) {
+    if (!cnt[i].emit) continue;
+    uint64_t oi = base[3 * i], at = base[3 * i + 2];
+    const uint64_t first = base[3 * i + 1];
+    uint32_t b = 0, lcp;
+    const MrgCount c = src_item(in, pr, i, &b, &lcp);
+    if (b || c.emit != base[3 * i + 3] - oi || c.recs != base[3 * i + 4] - first ||
+        c.blob != base[3 * i + 5] - at)
+      continue;  // (never: the count pass's walk)
+    const pfscdc_index_entry e = in.entries[i];
+    const uint8_t* s = (const uint8_t*)in.blob + e.path_off;
+    const uint32_t n = e.path_len;
+    uint32_t depth = 0;  // the '/' in s[0, k): a path's depth is that of its bytes but the last
+    for (uint32_t k = 0; k < lcp; k++) depth += s[k] == '/';
+    for (uint32_t k = lcp; k + 1 < n; k++) {
+      if (s[k] != '/') continue;
+      if (src_selected(pr, s, k + 1)) {  // dirFile.Index(): Index{Path: dir, File: {}}
+        pfscdc_index_entry o;
+        o.path_off = at;
+        o.tag_off = at + k + 2;
+        o.last_path_off = at + k + 3;
+        o.path_len = k + 1;
+        o.tag_len = o.last_path_len = 0;
+        o.flags = PFSCDC_IDX_HAS_FILE;
+        o.first = (uint32_t)first;
+        o.count = 0;
+        o.size_bytes = o.range_offset = 0;
+        for (uint32_t x = 0; x <= k; x++) blob[at + x] = (char)s[x];
+        blob[at + k + 1] = blob[at + k + 2] = blob[at + k + 3] = 0;
+        at += (uint64_t)k + 4;
+        entries[oi] = o;
+        meta[oi] = SrcMeta{kSrcDir, depth, 0};
+        infos[oi].size = 0;
+        infos[oi].type = PFSCDC_FILE_TYPE_DIR;
+        infos[oi].flags = src_child(pr, s, k + 1);
+        sizes[oi] = MrgCount{0, 0, 0};
+        atomicMax(maxdepth, depth);
+        atomicAdd(maxdepth + 1, 1u);  // directories inserted
+        oi++;
+      }
+      depth++;
+    }
+    if (!src_selected(pr, s, n)) continue;
+    const char* src = in.blob;
+    pfscdc_index_entry o = e;
+    o.path_off = at;
+    for (uint32_t x = 0; x < n; x++) blob[at + x] = (char)s[x];
+    at += n;
+    blob[at++] = 0;
+    o.tag_off = at;
+    for (uint32_t x = 0; x < e.tag_len; x++) blob[at + x] = src[e.tag_off + x];
+    at += e.tag_len;
+    blob[at++] = 0;
+    o.last_path_off = at;
+    for (uint32_t x = 0; x < e.last_path_len; x++) blob[at + x] = src[e.last_path_off + x];
+    at += e.last_path_len;
+    blob[at] = 0;
+    o.first = (uint32_t)first;
+    entries[oi] = o;
+    if (e.count) copy[i] = MrgCopy{(uint32_t)first, e.count, e.first, 0};
+    const bool dir = n && s[n - 1] == '/';
+    meta[oi] = SrcMeta{(uint32_t)i, depth, 0};
+    infos[oi].size = dir ? 0 : e.size_bytes;
+    infos[oi].type = dir ? PFSCDC_FILE_TYPE_DIR : PFSCDC_FILE_TYPE_FILE;
+    infos[oi].flags = src_child(pr, s, n);
+    sizes[oi] = MrgCount{0, 0, dir ? 0 : (uint64_t)e.size_bytes};
+    atomicMax(maxdepth, depth);
+  }
+}
+
+__global__ __launch_bounds__(kIdxBlock) void src_tree_kernel(
+    RtarList out, SrcMeta* __restrict__ meta, const uint64_t* __restrict__ sbase,
+    pfscdc_file_info* __restrict__ infos) {
+  for (uint64_t o = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; o < out.n;
+       o += (uint64_t)gridDim.x * kIdxBlock) {
+    uint64_t end = o + 1;
+    if (infos[o].type == PFSCDC_FILE_TYPE_DIR) {
+      const pfscdc_index_entry e = out.entries[o];
+      const uint8_t* s = (const uint8_t*)out.blob + e.path_off;
+      uint64_t lo = o + 1, hi = out.n;  // the first entry after o without o's path as a prefix
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        const pfscdc_index_entry q = out.entries[mid];
+        const uint8_t* t = (const uint8_t*)out.blob + q.path_off;
+        bool pre = q.path_len >= e.path_len;
+        for (uint32_t k = 0; pre && k < e.path_len; k++) pre = s[k] == t[k];
+        if (pre) lo = mid + 1;
+        else hi = mid;
+      }
+      end = lo;
+      infos[o].size = (int64_t)(sbase[3 * end + 2] - sbase[3 * o + 2]);
+    }
+    meta[o].end = end;
+  }
+}
+
+PFS_DEV pfscdc_segment src_segment(uint64_t offset, uint64_t size) {
+  pfscdc_segment sg;
+  sg.offset = offset;
+  sg.size = size;
+  sg.file = 0;
+  sg.flags = PFSCDC_SEG_VALID;
+  for (int k = 0; k < 32; k++) sg.hash[k] = 0;
+  return sg;
+}
+
+__global__ __launch_bounds__(kIdxBlock) void src_leaf_kernel(RtarList out,
+                                                             uint8_t* __restrict__ buf,
+                                                             pfscdc_segment* __restrict__ segs) {
+  const uint64_t items = out.n > out.nr ? out.n : out.nr;
+  for (uint64_t x = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; x < items;
+       x += (uint64_t)gridDim.x * kIdxBlock) {
+    if (x < out.nr) {  // hashDataRefs: the DataRefs' hashes back to back
+      const uint4* h = reinterpret_cast<const uint4*>(out.drs[x].data.hash);
+      uint4* d = reinterpret_cast<uint4*>(buf + 32 * x);
+      d[0] = h[0];
+      d[1] = h[1];
+    }
+    if (x < out.n) segs[x] = src_segment(32ull * out.entries[x].first, 32ull * out.entries[x].count);
+  }
+}
+
+// The caller's leaf hashes (32 bytes per input entry) as the files' hashes.
+__global__ __launch_bounds__(kIdxBlock) void src_leaf_copy_kernel(
+    const SrcMeta* __restrict__ meta, const uint8_t* __restrict__ leaf, uint64_t n,
+    pfscdc_file_info* __restrict__ infos) {
+  for (uint64_t o = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; o < n;
+       o += (uint64_t)gridDim.x * kIdxBlock) {
+    if (infos[o].type == PFSCDC_FILE_TYPE_DIR) continue;
+    for (int k = 0; k < 32; k++) infos[o].hash[k] = leaf[32ull * meta[o].src + k];
+  }
+}
+
+__global__ __launch_bounds__(kIdxBlock) void src_level_count_kernel(
+    const SrcMeta* __restrict__ meta, const pfscdc_file_info* __restrict__ infos, uint64_t n,
+    uint32_t level, MrgCount* __restrict__ cnt) {
+  for (uint64_t o = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; o < n;
+       o += (uint64_t)gridDim.x * kIdxBlock)
+    cnt[o] = MrgCount{meta[o].depth == level + 1 ? 1u : 0u,
+                      meta[o].depth == level && infos[o].type == PFSCDC_FILE_TYPE_DIR ? 1u : 0u, 0};
+}
+
+__global__ __launch_bounds__(kIdxBlock) void src_level_gather_kernel(
+    const SrcMeta* __restrict__ meta, const pfscdc_file_info* __restrict__ infos,
+    const uint64_t* __restrict__ base, uint64_t n, uint32_t level, uint8_t* __restrict__ buf,
+    pfscdc_segment* __restrict__ segs) {
+  for (uint64_t o = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; o < n;
+       o += (uint64_t)gridDim.x * kIdxBlock) {
+    const SrcMeta m = meta[o];
+    if (m.depth == level + 1) {
+      const uint4* h = reinterpret_cast<const uint4*>(infos[o].hash);
+      uint4* d = reinterpret_cast<uint4*>(buf + 32 * base[3 * o]);
+      d[0] = h[0];
+      d[1] = h[1];
+    }
+    if (m.depth == level && infos[o].type == PFSCDC_FILE_TYPE_DIR) {
+      // its children: the entries of depth level + 1 in (o, end)
+      const uint64_t a = base[3 * (o + 1)], b = base[3 * m.end];
+      segs[base[3 * o + 1]] = src_segment(32 * a, 32 * (b - a));
+    }
+  }
+}
+
+// level < 0: the leaf pass's digests (segs[o]) into the files' infos; else the digests of the
+// directories of depth level (segs[their number among them]) into theirs.
+__global__ __launch_bounds__(kIdxBlock) void src_scatter_kernel(
+    const SrcMeta* __restrict__ meta, const uint64_t* __restrict__ base,
+    const pfscdc_segment* __restrict__ segs, uint64_t n, int level,
+    pfscdc_file_info* __restrict__ infos) {
+  for (uint64_t o = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; o < n;
+       o += (uint64_t)gridDim.x * kIdxBlock) {
+    const bool dir = infos[o].type == PFSCDC_FILE_TYPE_DIR;
+    if (level < 0 ? dir : (!dir || meta[o].depth != (uint32_t)level)) continue;
+    const pfscdc_segment* sg = &segs[level < 0 ? o : base[3 * o + 1]];
+    for (int k = 0; k < 32; k++) infos[o].hash[k] = sg->hash[k];
+  }
+}
+
+hipError_t launch_src_count(const RtarList& in, const SrcPred& pr, MrgCount* cnt, uint32_t* bad,
+                            int num_cus, hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  src_count_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(in, pr, cnt, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_src_fill(const RtarList& in, const SrcPred& pr, const MrgCount* cnt,
+                           const uint64_t* base, pfscdc_index_entry* entries, char* blob,
+                           MrgCopy* copy, SrcMeta* meta, pfscdc_file_info* infos, MrgCount* sizes,
+                           uint32_t* maxdepth, pfscdc_full_dataref* drs, int num_cus,
+                           hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  src_fill_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(
+      in, pr, cnt, base, entries, blob, copy, meta, infos, sizes, maxdepth);
+  merge_copy_kernel<<<merge_grid(in.n * 8, num_cus), kIdxBlock, 0, st>>>(
+      (const uint4*)in.drs, copy, in.n, (uint4*)drs);
+  return hipGetLastError();
+}
+
+hipError_t launch_src_tree(const RtarList& out, SrcMeta* meta, const uint64_t* sbase,
+                           pfscdc_file_info* infos, int num_cus, hipStream_t st) {
+  if (out.n == 0) return hipSuccess;
+  src_tree_kernel<<<merge_grid(out.n, num_cus), kIdxBlock, 0, st>>>(out, meta, sbase, infos);
+  return hipGetLastError();
+}
+
+hipError_t launch_src_leaf(const RtarList& out, uint8_t* buf, pfscdc_segment* segs, int num_cus,
+                           hipStream_t st) {
+  if (out.n == 0) return hipSuccess;
+  src_leaf_kernel<<<merge_grid(out.n > out.nr ? out.n : out.nr, num_cus), kIdxBlock, 0, st>>>(
+      out, buf, segs);
+  return hipGetLastError();
+}
+
+hipError_t launch_src_leaf_copy(const SrcMeta* meta, const uint8_t* leaf, uint64_t n,
+                                pfscdc_file_info* infos, int num_cus, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  src_leaf_copy_kernel<<<merge_grid(n, num_cus), kIdxBlock, 0, st>>>(meta, leaf, n, infos);
+  return hipGetLastError();
+}
+
+hipError_t launch_src_level_count(const SrcMeta* meta, const pfscdc_file_info* infos, uint64_t n,
+                                  uint32_t level, MrgCount* cnt, int num_cus, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  src_level_count_kernel<<<merge_grid(n, num_cus), kIdxBlock, 0, st>>>(meta, infos, n, level, cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_src_level_gather(const SrcMeta* meta, const pfscdc_file_info* infos,
+                                   const uint64_t* base, uint64_t n, uint32_t level, uint8_t* buf,
+                                   pfscdc_segment* segs, int num_cus, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  src_level_gather_kernel<<<merge_grid(n, num_cus), kIdxBlock, 0, st>>>(meta, infos, base, n, level,
+                                                                        buf, segs);
+  return hipGetLastError();
+}
+
+hipError_t launch_src_scatter(const SrcMeta* meta, const uint64_t* base, const pfscdc_segment* segs,
+                              uint64_t n, int level, pfscdc_file_info* infos, int num_cus,
+                              hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  src_scatter_kernel<<<merge_grid(n, num_cus), kIdxBlock, 0, st>>>(meta, base, segs, n, level,
+                                                                   infos);
+  return hipGetLastError();
+}
+
 }  // namespace pfscdc

@@ -172,6 +172,7 @@ struct pfscdc_ctx {
   IndexStats index_stats;             // the last pfscdc_index_read
   MergeStats merge_stats;             // the last pfscdc_index_merge_ctx
   ResidentStats resident_stats;       // the last calls over device-resident lists
+  SourceStats source_stats;           // the last pfscdc_source_open
 };
 
 namespace pfscdc {
@@ -179,6 +180,7 @@ const pfscdc_params& ctx_params(const pfscdc_ctx* ctx) { return ctx->params; }
 IndexStats& ctx_index_stats(pfscdc_ctx* ctx) { return ctx->index_stats; }
 MergeStats& ctx_merge_stats(pfscdc_ctx* ctx) { return ctx->merge_stats; }
 ResidentStats& ctx_resident_stats(pfscdc_ctx* ctx) { return ctx->resident_stats; }
+SourceStats& ctx_source_stats(pfscdc_ctx* ctx) { return ctx->source_stats; }
 int ctx_num_cus(const pfscdc_ctx* ctx) { return ctx->num_cus; }
 }  // namespace pfscdc
 

@@ -47,7 +47,7 @@ enum class Knob : int {
   HashBinBytes, HashWaves, HashFair, HashFairEvery,
   RefIdSplit, CommitTwoSets, CommitLongPct,
   UwWorkers, UwInflight, UwMirror, UwIndexGrouped, UwArenaPoolBytes, CtxCache, CopyThreads,
-  IndexDecode, IndexMerge, Trace,
+  IndexDecode, IndexMerge, Source, Trace,
   kCount
 };
 int64_t knob(Knob k);
@@ -454,6 +454,64 @@ hipError_t launch_rtar_pieces(const RtarPieces& p, MrgCount* cnt, const uint64_t
 hipError_t launch_rtar_chunks(pfscdc_slice* slices, uint64_t m, const uint32_t* table,
                               const uint64_t* chunk_offs, uint32_t nchunks, uint32_t* bad, int num_cus,
                               hipStream_t st);
+
+// ---- the Source on the device (source_dev.cpp; kernels in cdc_kernels.hip §11) ----
+struct SrcPred {  // SrcArg (source.h) with its strings on the device
+  const char *name, *dir;
+  uint32_t name_len, dir_len;
+  uint32_t all, exclude_dir, child_flag, reserved;
+};
+enum SrcBad : uint32_t {  // what the count pass found in the input
+  kSrcUnordered = 1,  // not in (path, tag) order                    } the host arm
+  kSrcUnclean = 2,    // a path that is not IsClean(p, IsDir(p))     } takes the
+  kSrcDirTwice = 4,   // one directory path twice                    } call
+  kSrcMalformed = 8,  // strings or DataRefs outside the arrays: PFSCDC_EINVAL
+  kSrcNotLevel0 = 16, // an entry with a Range: PFSCDC_EINVAL
+};
+constexpr uint32_t kSrcDir = 0xffffffffu;  // SrcMeta::src of an inserted directory
+struct SrcMeta {  // per output entry
+  uint32_t src;    // the input entry it is, or kSrcDir
+  uint32_t depth;  // the '/' in its path but for the last byte: "/" 0, "/a" and "/a/" 1
+  uint64_t end;    // a directory's subtree is entries (own index, end); a file's end = index + 1
+};
+// cnt[i] = {entries, DataRefs, blob bytes} input entry i emits; *bad |= SrcBad (zeroed before)
+hipError_t launch_src_count(const RtarList& in, const SrcPred& pr, MrgCount* cnt, uint32_t* bad,
+                            int num_cus, hipStream_t st);
+// after launch_merge_scan of cnt into base: the output entries, their strings, meta (end unset),
+// the infos' type, flags and file size, sizes[o] = {0, 0, file size}, maxdepth[0] and the
+// directories inserted in maxdepth[1] (both zeroed before),
+// copy[] (zeroed before) and through it the selected files' DataRefs into drs
+hipError_t launch_src_fill(const RtarList& in, const SrcPred& pr, const MrgCount* cnt,
+                           const uint64_t* base, pfscdc_index_entry* entries, char* blob,
+                           MrgCopy* copy, SrcMeta* meta, pfscdc_file_info* infos, MrgCount* sizes,
+                           uint32_t* maxdepth, pfscdc_full_dataref* drs, int num_cus,
+                           hipStream_t st);
+// after launch_merge_scan of sizes into sbase: meta[].end and the directories' sizes
+hipError_t launch_src_tree(const RtarList& out, SrcMeta* meta, const uint64_t* sbase,
+                           pfscdc_file_info* infos, int num_cus, hipStream_t st);
+// buf[32 k ...] = DataRef k's hash; segs[o] = entry o's DataRef hashes as one hash record
+hipError_t launch_src_leaf(const RtarList& out, uint8_t* buf, pfscdc_segment* segs, int num_cus,
+                           hipStream_t st);
+hipError_t launch_src_leaf_copy(const SrcMeta* meta, const uint8_t* leaf, uint64_t n,
+                                pfscdc_file_info* infos, int num_cus, hipStream_t st);
+// cnt[o] = {depth == level + 1, directory of depth level, 0}
+hipError_t launch_src_level_count(const SrcMeta* meta, const pfscdc_file_info* infos, uint64_t n,
+                                  uint32_t level, MrgCount* cnt, int num_cus, hipStream_t st);
+// after launch_merge_scan of cnt into base: the children's hashes into buf, one record per
+// directory of depth level into segs
+hipError_t launch_src_level_gather(const SrcMeta* meta, const pfscdc_file_info* infos,
+                                   const uint64_t* base, uint64_t n, uint32_t level, uint8_t* buf,
+                                   pfscdc_segment* segs, int num_cus, hipStream_t st);
+// the digests into the infos: level < 0 the leaf pass's, else those of depth level's directories
+hipError_t launch_src_scatter(const SrcMeta* meta, const uint64_t* base, const pfscdc_segment* segs,
+                              uint64_t n, int level, pfscdc_file_info* infos, int num_cus,
+                              hipStream_t st);
+// what pfscdc_last_source_stats / pfscdc_last_source_timings report
+struct SourceStats {
+  uint64_t n[8] = {};
+  float ms[4] = {};
+};
+SourceStats& ctx_source_stats(pfscdc_ctx* ctx);
 
 hipError_t launch_synth(uint8_t* out, const uint64_t* offs, uint32_t nfiles, const uint32_t* ids,
                         const uint64_t* starts, uint64_t seed, uint32_t mode, hipStream_t st);

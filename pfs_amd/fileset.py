@@ -547,6 +547,152 @@ class _DevTarStream(TarStream):
         return nw.value
 
 
+FILE, DIR = _lib.FILE_TYPE_FILE, _lib.FILE_TYPE_DIR
+
+
+@dataclass
+class FileInfo:
+    """``pfs.FileInfo`` as ``source.Iterate`` computes it: ``type`` is ``FILE`` or ``DIR`` (the
+    path ends in '/'), ``size`` a file's bytes or the sum over a directory's subtree, ``hash``
+    a file's ``hashDataRefs`` (or ``MergeFileReader.Hash``) or BLAKE2b-256 over a directory's
+    immediate children's hashes."""
+    path: str
+    tag: str
+    type: int
+    size: int
+    hash: bytes
+
+
+def _leaf_ptr(leaf):
+    if leaf is None:
+        return None, None, 0
+    if hasattr(leaf, "data_ptr"):  # a torch uint8 tensor
+        return leaf.data_ptr() if leaf.numel() else None, leaf, int(leaf.is_cuda)
+    buf = (C.c_uint8 * max(1, len(leaf))).from_buffer_copy(bytes(leaf) or b"\0")
+    return C.cast(buf, C.c_void_p), buf, 0
+
+
+def source_host(lst: Optional[IndexList], kind: int, arg: str = "", leaf=None):
+    """pfscdc_source_host: the Source of a level-0 list on the host, ``(IndexList, infos)`` with
+    one (hash, size, type, flags) per entry.  ``leaf``: 32 bytes per entry of ``lst`` used as
+    the files' hashes.  KeyError where the reference answers file-not-found."""
+    lib = _lib.load()
+    out, infos = C.c_void_p(), C.POINTER(_lib.FileInfoC)()
+    ptr, keep, _ = _leaf_ptr(leaf)
+    rc = lib.pfscdc_source_host(lst._p if lst is not None else None, kind,
+                                arg.encode("utf-8", "surrogateescape"), ptr, C.byref(out),
+                                C.byref(infos))
+    del keep
+    if rc:
+        msg = lib.pfscdc_source_host_error().decode("utf-8", "replace")
+        if rc == _lib.PFSCDC_ENOTFOUND:
+            raise KeyError(msg)
+        raise _lib.PfsCdcError(rc, msg)
+    res = IndexList(out)
+    try:
+        got = [(bytes(infos[i].hash), infos[i].size, infos[i].type, infos[i].flags)
+               for i in range(len(res))]
+    finally:
+        lib.pfscdc_file_infos_free(infos)
+    return res, got
+
+
+class _BorrowedDevList(DevIndexList):
+    """A source's list: owned by the source, which it keeps alive."""
+
+    def __init__(self, ptr, device, owner):
+        super().__init__(ptr, device)
+        self._owner = owner
+
+    def free(self) -> None:
+        self._p = None
+        self._owner = None
+
+
+class Source:
+    """An owned pfscdc_source: the selected entries with their directories as a resident list
+    (``list``: what the tar calls take) and one FileInfo record per entry on the GPU."""
+
+    def __init__(self, ptr, device: int):
+        self.lib = _lib.load()
+        self._p = ptr
+        self.device = device
+
+    def __len__(self) -> int:
+        return int(self.lib.pfscdc_source_count(self._p))
+
+    @property
+    def list(self) -> DevIndexList:
+        return _BorrowedDevList(self.lib.pfscdc_source_list(self._p), self.device, self)
+
+    def infos(self, chunker=None) -> list:
+        """(hash, size, type, flags) per entry."""
+        c = chunker if chunker is not None else Chunker(ChunkParams(), self.device)
+        try:
+            n = len(self)
+            arr = (_lib.FileInfoC * max(1, n))()
+            rc = c.lib.pfscdc_source_infos(c.ctx, self._p, arr)
+        finally:
+            if chunker is None:
+                c.close()
+        if rc:
+            raise _lib.PfsCdcError(rc, "pfscdc_source_infos")
+        return [(bytes(arr[i].hash), arr[i].size, arr[i].type, arr[i].flags) for i in range(n)]
+
+    def free(self) -> None:
+        if self._p:
+            self.lib.pfscdc_source_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def source_open(chunker, lst, kind: int, arg: str = "", leaf=None) -> Source:
+    """pfscdc_source_open over a ``DevIndexList`` (pfscdc_source_open_list over an ``IndexList``
+    or None, uploaded first): on the device or on the host by the PFSCDC_SOURCE knob, with the
+    same result either way.  ``leaf``: bytes or a torch uint8 tensor (host or device), 32 bytes
+    per entry of ``lst``.  KeyError where the reference answers file-not-found."""
+    out = C.c_void_p()
+    ptr, keep, on_dev = _leaf_ptr(leaf)
+    fn = chunker.lib.pfscdc_source_open if isinstance(lst, DevIndexList) \
+        else chunker.lib.pfscdc_source_open_list
+    rc = fn(chunker.ctx, lst._p if lst is not None else None, kind,
+            arg.encode("utf-8", "surrogateescape"), ptr, on_dev, C.byref(out))
+    del keep
+    if rc:
+        msg = chunker.lib.pfscdc_last_error(chunker.ctx)
+        msg = msg.decode("utf-8", "replace") if msg else ""
+        if rc == _lib.PFSCDC_ENOTFOUND:
+            raise KeyError(msg)
+        raise _lib.PfsCdcError(rc, msg)
+    return Source(out, chunker.device)
+
+
+def last_source_stats(chunker) -> dict:
+    """Counts and stage times (ms) of the last source_open on ``chunker``'s context."""
+    n, ms = (C.c_uint64 * 8)(), (C.c_float * 4)()
+    chunker.lib.pfscdc_last_source_stats(chunker.ctx, n)
+    chunker.lib.pfscdc_last_source_timings(chunker.ctx, ms)
+    out = dict(zip(["device", "entries_in", "entries_out", "dirs_inserted", "levels",
+                    "hash_launches", "h2d_bytes", "d2h_bytes"], [int(x) for x in n]))
+    out.update(zip(["select_ms", "tree_ms", "leaf_ms", "levels_ms"],
+                   [round(float(x), 4) for x in ms]))
+    return out
+
+
+class _SourceTarStream(_DevTarStream):
+    """GetFileTAR as the reference serves it: one tar entry per entry of a source's stream,
+    directories included."""
+
+    def __init__(self, storage, source: Source):
+        self._source = source
+        super().__init__(storage, source.list)
+
+
 class _FlatRefs:
     """The DataRefs of an IndexList as TarStream looks at them: their count, and their Ref
     ids when a missing chunk has to be named."""
@@ -595,8 +741,11 @@ class FileSet:
     """The merged view of opened filesets (``Storage.open``): the files that
     ``MergeReader.iterate`` yields, in path-then-tag order."""
 
-    def __init__(self, storage, merged: Optional[IndexList], resident: Optional[DevIndexList] = None):
+    def __init__(self, storage, merged: Optional[IndexList], resident: Optional[DevIndexList] = None,
+                 nfilesets: int = 1):
         self._storage, self._host, self._dev = storage, merged, resident
+        self._nfilesets = nfilesets
+        self._leaf = None  # MergeFileReader.Hash per file, made on first use
 
     @property
     def _list(self) -> IndexList:
@@ -628,6 +777,62 @@ class FileSet:
         if self._dev is not None:
             return _DevTarStream(self._storage, self._dev)
         return _ListTarStream(self._storage, self._list)
+
+    # ---- the file RPCs over a Source (driver_file.go:173-385)
+
+    def _source(self, kind: int, arg: str) -> Source:
+        """The opened filesets wrapped in a Source.  A resident fileset feeds its list straight
+        in, a host one uploads; opened over more than one fileset the files' hashes are
+        ``MergeFileReader.Hash`` (storage.go:124-127), else ``hashDataRefs`` on the device."""
+        if self._nfilesets > 1 and self._leaf is None:
+            from .chunk import merge_file_hash
+            self._leaf = b"".join(
+                bytes(32) if f.path.endswith("/") else
+                merge_file_hash(self._storage.store, f.data_refs, self._storage.device)
+                for f in self.files())
+        leaf = self._leaf
+        c = Chunker(ChunkParams(), self._storage.device)
+        try:
+            return source_open(c, self._dev if self._dev is not None else self._host, kind, arg,
+                               leaf)
+        finally:
+            c.close()
+
+    def _infos(self, kind: int, arg: str, children: bool = False) -> list:
+        src = self._source(kind, arg)
+        try:
+            raw, infos = src.list.download().raw(), src.infos()
+        finally:
+            src.free()
+        return [FileInfo(d["path"].decode("utf-8", "surrogateescape"),
+                         d["tag"].decode("utf-8", "surrogateescape"), t, size, h)
+                for d, (h, size, t, flags) in zip(raw, infos)
+                if not children or flags & _lib.INFO_CHILD]
+
+    def walk_file(self, p: str = "") -> list:
+        """``walkFile``: the ``FileInfo`` of ``p`` and of everything below it, directories
+        included ("" or "/": the whole commit; an empty commit gives []).  KeyError if nothing
+        is there."""
+        return self._infos(_lib.SRC_SUBTREE, p)
+
+    def list_file(self, p: str = "") -> list:
+        """``listFile``: the ``FileInfo`` of the immediate children of directory ``p`` (of the
+        file ``p`` itself, if it is one)."""
+        return self._infos(_lib.SRC_LIST, p, children=True)
+
+    def inspect_file(self, p: str = "") -> Optional[FileInfo]:
+        """``inspectFile``: the ``FileInfo`` of ``p`` (the last entry with path ``p`` or
+        ``p + "/"``).  KeyError if nothing is there."""
+        q = clean(p, False)
+        q = "" if q == "/" else q
+        hits = [fi for fi in self._infos(_lib.SRC_SUBTREE, p) if fi.path in (q, q + "/")]
+        return hits[-1] if hits else None
+
+    def get_file(self, p: str) -> TarStream:
+        """``getFile`` of a literal path as ``GetFileTAR`` serves it: ``p`` (a file, or a
+        directory with everything below it) as a ``TarStream`` with one entry per entry of the
+        source, directories included.  KeyError if nothing is there."""
+        return _SourceTarStream(self._storage, self._source(_lib.SRC_GET, p))
 
 
 class Storage:
@@ -681,7 +886,7 @@ class Storage:
                     a.free()
             finally:
                 c.close()
-            return FileSet(self, None, merged)
+            return FileSet(self, None, merged, nfilesets=len(roots))
         try:
             pairs = [(index_read(c, self.store, d, lower, upper, prefix, tag),
                       index_read(c, self.store, a, lower, upper, prefix, tag))
@@ -689,7 +894,7 @@ class Storage:
             merged = index_merge(pairs, chunker=c)
         finally:
             c.close()
-        return FileSet(self, merged)
+        return FileSet(self, merged, nfilesets=len(roots))
 
     def shard(self, filesets, threshold: int = 10 ** 9) -> list:
         """``Storage.Shard`` (shard.go:12-18): the (lower, upper) path ranges, "" an open end,

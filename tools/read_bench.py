@@ -55,7 +55,16 @@ window's runs.
 Every resident window is compared with the host hand-over's bytes.  Writes
 profiles/r11/resident/resident.json.
 
-usage: python tools/read_bench.py [--tar | --index | --merge | --compact | --resident]
+--source: the Source (pfscdc_source_open: directory entries, path predicate, FileInfo) over the
+index lists of --index's two commits (65,536 files of 4 KiB, --files files of 256 B), laid out
+over a directory tree of fan-out 64 and flat, as a resident input: SUBTREE("") and GET of one
+second-level directory (flat: of the one directory), the device arm (PFSCDC_SOURCE=1) and the
+host arm (0) alternating call by call.  Per arm: median, min and max of each stage's (insert and
+select, sizes, leaf hashes, the directory levels) and the whole call's wall time, and the stats'
+counts and bytes each way.  Every device result is compared with the host arm's, array for array
+and info for info.  Writes profiles/r12/source/source.json.
+
+usage: python tools/read_bench.py [--tar | --index | --merge | --compact | --resident | --source]
                                   [--chunks N]
                                   [--chunk-bytes B] [--files N] [--reps R] [--warmup W]
                                   [--out PATH]"""
@@ -561,12 +570,114 @@ def compact_rows(args):
     return [row]
 
 
+def source_list(n, fbytes, flat, seed):
+    """A level-0 list of n files of one DataRef of fbytes bytes each, in path order: over a
+    directory tree of fan-out 64 (/b/AA/BB/CC/fNNNNNNN, the directories the base-64 digits of N)
+    or flat (/b/fNNNNNNN).  Fixed-layout frames assembled with numpy, as synthetic_lists does."""
+    from pfs_amd import fileset as PF
+    ids = np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(seed)
+    L = 11 if flat else 20
+    a = np.zeros((n, 8 + L + 131), dtype=np.uint8)
+    a[:, 0] = L + 131  # int64 LE frame length
+    a[:, 8:10] = (0x0A, L)  # path
+    at = 10
+    a[:, at:at + 3] = np.frombuffer(b"/b/", dtype=np.uint8)
+    at += 3
+    if not flat:
+        for shift in (18, 12, 6):
+            d = (ids >> shift) & 63
+            a[:, at] = 48 + d // 10
+            a[:, at + 1] = 48 + d % 10
+            a[:, at + 2] = 0x2F
+            at += 3
+    a[:, at] = ord("f")
+    for k in range(7):
+        a[:, at + 1 + k] = 48 + (ids // 10 ** (6 - k)) % 10
+    at += 8
+    a[:, at:at + 4] = (0x1A, 127, 0x0A, 7)  # file { tag
+    a[:, at + 4:at + 11] = np.frombuffer(b"default", dtype=np.uint8)
+    a[:, at + 11:at + 17] = (0x12, 116, 0x0A, 73, 0x0A, 32)  # data_refs { ref { id
+    a[:, at + 17:at + 49] = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    a[:, at + 49:at + 54] = (0x10, 0x80, 0xA4, 0xE8, 0x03)  # Ref.size_bytes 8,000,000
+    a[:, at + 54:at + 56] = (0x22, 32)  # dek
+    a[:, at + 56:at + 88] = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    a[:, at + 88:at + 90] = (0x12, 32)  # hash
+    a[:, at + 90:at + 122] = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    off = 16384 + 256 * (ids % 8000)  # offset_bytes: a three-byte varint
+    a[:, at + 122] = 0x18
+    a[:, at + 123] = (off & 0x7F) | 0x80
+    a[:, at + 124] = ((off >> 7) & 0x7F) | 0x80
+    a[:, at + 125] = off >> 14
+    assert fbytes in (256, 4096)  # size_bytes: a two-byte varint
+    a[:, at + 126:at + 129] = (0x20, 0x80, fbytes >> 7)
+    return PF.index_decode_host(a.tobytes())
+
+
+def source_rows(args):
+    """--source: the Source (directory entries, predicate, FileInfo) over the index lists of
+    --index's two commits, laid out over a tree of fan-out 64 and flat: SUBTREE("") and GET of
+    one second-level directory (flat: of /b), the device arm (PFSCDC_SOURCE=1) and the host arm
+    (0) alternating call by call over a resident input; every device result is compared with
+    the host arm's, array for array and info for info."""
+    import time
+
+    from pfs_amd import fileset as PF
+    rows = []
+    keys = ["select_ms", "tree_ms", "leaf_ms", "levels_ms", "wall_ms"]
+    shapes = [(65536, 4096), (args.files, 256)] if args.files != 65536 else [(65536, 4096)]
+    for nfiles, fbytes in shapes:
+        for flat in (False, True):
+            lst = source_list(nfiles, fbytes, flat, nfiles)
+            c = Chunker(ChunkParams(), 0)
+            dev = PF.DevIndexList.upload(c, lst)
+            for kind, arg in ((_lib.SRC_SUBTREE, ""), (_lib.SRC_GET, "/b" if flat else "/b/00/01")):
+                runs = {1: [], 0: []}
+                last = {}
+                for i in range(args.warmup + args.reps):
+                    for arm in (1, 0):
+                        _lib.set_knob("PFSCDC_SOURCE", arm)
+                        t0 = time.perf_counter()
+                        src = PF.source_open(c, dev, kind, arg)
+                        wall = (time.perf_counter() - t0) * 1e3
+                        stats = PF.last_source_stats(c)
+                        if stats["device"] != arm:
+                            raise SystemExit("read_bench: the wrong arm ran")
+                        got = src.list.download(c)
+                        last[arm] = (list_arrays(got), src.infos(c))
+                        got.free()
+                        src.free()
+                        if arm == 0 and last[0] != last[1]:
+                            raise SystemExit("read_bench: the device arm's result differs from the host arm's")
+                        if i >= args.warmup:
+                            stats["wall_ms"] = wall
+                            runs[arm].append(stats)
+                row = {"files": nfiles, "file_bytes": fbytes, "layout": "flat" if flat else "fanout64",
+                       "predicate": ["ALL", "SUBTREE", "LIST", "GET"][kind], "arg": arg,
+                       "reps": args.reps, "warmup": args.warmup, "device_equals_host": True}
+                for arm, name in ((1, "device"), (0, "host")):
+                    r = runs[arm]
+                    row[name] = {k: {"median": round(statistics.median(x[k] for x in r), 3),
+                                     "min": round(min(x[k] for x in r), 3),
+                                     "max": round(max(x[k] for x in r), 3)} for k in keys}
+                    row[name].update({k: r[0][k] for k in ("entries_in", "entries_out", "dirs_inserted",
+                                                           "levels", "hash_launches", "h2d_bytes",
+                                                           "d2h_bytes")})
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+            _lib.set_knob("PFSCDC_SOURCE", _lib.knob_info()["PFSCDC_SOURCE"][2])
+            dev.free()
+            c.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--index", action="store_true")
     ap.add_argument("--merge", action="store_true")
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--resident", action="store_true")
+    ap.add_argument("--source", action="store_true")
     ap.add_argument("--files", type=int, default=1 << 20)
     ap.add_argument("--tar", action="store_true")
     ap.add_argument("--chunks", type=int, default=1024)
@@ -588,6 +699,16 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/read_bench.py --" + what,
+                       "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
+            f.write("\n")
+        return
+    if args.source:
+        if args.out == os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json"):
+            args.out = os.path.join(ROOT, "profiles", "r12", "source", "source.json")
+        rows = source_rows(args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/read_bench.py --source",
                        "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
             f.write("\n")
         return
