@@ -127,7 +127,11 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
   // before is settled and its exit is chunk i's claim.  A chunk wholly inside one entry (its
   // one annotation gets Offset 0, index/writer.go:102-121) holds no frame start at all; any
   // other chunk with a wrong claim is walked again from the exit.  Each repeat settles a chunk.
-  uint64_t nf = 0;
+  // A length the walk cannot follow ends it (walk_err, in chunk settled - 1); the frames it did
+  // settle still go through the count pass, since the first frame that fails is the one to name
+  // and a frame in front of the bad length may fail to parse.
+  uint64_t nf = 0, walk_err = kIdxNone;
+  uint32_t settled = nc;
   for (uint32_t i = 0; i < nc; i++) {
     if (i > 0 && walks[i].start != outs[i - 1].exit) {
       st.n[1]++;
@@ -149,14 +153,18 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
     if (outs[i].err != kIdxNone) {
       // A frame that runs past a selection that ends before the level does is past the filter's
       // end (a wanted frame ends inside the tail chunk): the stream ends in front of it.
-      if (!(open_end && outs[i].past)) return corrupt(ctx, level, outs[i].err - start0);
-      for (uint32_t k = i + 1; k < nc; k++) outs[k] = IdxWalkOut{n, 0, kIdxNone, 0};
+      if (!(open_end && outs[i].past)) {
+        walk_err = outs[i].err;
+        settled = i + 1;
+      } else {
+        for (uint32_t k = i + 1; k < nc; k++) outs[k] = IdxWalkOut{n, 0, kIdxNone, 0};
+      }
       break;
     }
   }
   st.ms[2] += ms_since(t0);
   st.n[3] += nf;
-  if (nf == 0) return PFSCDC_OK;
+  if (nf == 0) return walk_err != kIdxNone ? corrupt(ctx, level, walk_err - start0) : PFSCDC_OK;
   if (nf > 0xffffffffull) return ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "more than 2^32 index entries");
   // ---- the decode: frame starts packed, count pass, prefix sums, fill pass
   t0 = Clock::now();
@@ -166,7 +174,7 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
   IDX_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 2 * (nf + 1)));
   IDX_HIP(ctx, d_err.alloc(sizeof(uint64_t)));
   uint64_t at = 0;
-  for (uint32_t i = 0; i < nc; at += outs[i].count, i++)
+  for (uint32_t i = 0; i < settled; at += outs[i].count, i++)
     if (outs[i].count)
       IDX_HIP(ctx, hipMemcpyAsync(d_fstart.as<uint64_t>() + at, d_starts.as<uint64_t>() + walks[i].slot,
                                   sizeof(uint64_t) * outs[i].count, hipMemcpyDeviceToDevice, s));
@@ -179,6 +187,7 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
   IDX_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 2 * nf, sizeof totals,
                               hipMemcpyDeviceToHost, s));
   IDX_HIP(ctx, hipStreamSynchronize(s));
+  h_err = std::min(h_err, walk_err);  // (every settled frame starts in front of walk_err)
   if (h_err != kIdxNone) return corrupt(ctx, level, h_err - start0);
   if (totals[0] > 0xffffffffull) return ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "more than 2^32 DataRefs");
   DevMem d_entries, d_drs, d_blob;
@@ -241,6 +250,9 @@ int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const
   std::vector<int64_t> off(nc);
   for (uint32_t i = 0; i < nc; i++) {
     const pfscdc_index_entry& e = cur.entries[parents[i]];
+    if ((uint64_t)e.first + e.count >= cur.drs.size())  // (select() saw PFSCDC_IDX_HAS_CHUNK_REF)
+      return ctx_fail(ctx, PFSCDC_ECORRUPT, "index level " + std::to_string(level) +
+                                                ": a Range's chunk_ref lies outside the list");
     refs[i] = cur.drs[e.first + e.count];
     off[i] = e.range_offset;
     if (refs[i].data.size_bytes < 0 || cb[i] + (uint64_t)refs[i].data.size_bytes < cb[i])
