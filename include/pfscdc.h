@@ -907,14 +907,17 @@ int pfscdc_last_resident_stats(pfscdc_ctx* ctx, uint64_t out[8]);
  * entry per entry of the stream, directories (typeflag 5) included: GetFileTAR as served.
  * Predicates (arg goes through cleanPath here; "" and "/" name the root):
  *   PFSCDC_SRC_ALL      everything (arg ignored);
- *   PFSCDC_SRC_SUBTREE  inspectFile / walkFile / diffFile: path == p || HasPrefix(path, p + "/"),
+ *   PFSCDC_SRC_SUBTREE  inspectFile / walkFile: path == p || HasPrefix(path, p + "/"),
  *                       p = cleanPath(arg), "" for the root;
  *   PFSCDC_SRC_LIST     listFile: not Clean(name, true) itself, else path == name or
  *                       HasPrefix(path, Clean(name, true)); PFSCDC_INFO_CHILD is set in the flags
  *                       of the entries with pathIsChild(name, cleanPath(path));
  *   PFSCDC_SRC_GET      getFile's `full` filter for a literal glob: path == glob, path == glob + "/"
  *                       or HasPrefix(path, glob + "/"); "/" selects everything.  A glob holding one
- *                       of *?[]{}!()@+^ or a backslash: PFSCDC_EUNSUPPORTED with the glob named.
+ *                       of *?[]{}!()@+^ or a backslash: PFSCDC_EUNSUPPORTED with the glob named;
+ *   PFSCDC_SRC_DIFF     diffFile: SUBTREE's predicate and cleaning, but neither side of a diff is
+ *                       wrapped in NewErrOnEmpty (driver_file.go:356-383): nothing selected is
+ *                       PFSCDC_OK with no entries.
  * PFSCDC_ENOTFOUND (NewErrOnEmpty): nothing selected by GET, or by SUBTREE with p != "".
  * PFSCDC_EINVAL: an entry with a Range (not a level-0 list), or strings / DataRefs outside the
  * list's arrays. */
@@ -922,6 +925,7 @@ int pfscdc_last_resident_stats(pfscdc_ctx* ctx, uint64_t out[8]);
 #define PFSCDC_SRC_SUBTREE 1
 #define PFSCDC_SRC_LIST 2
 #define PFSCDC_SRC_GET 3
+#define PFSCDC_SRC_DIFF 4
 #define PFSCDC_FILE_TYPE_FILE 1u /* pfs.FileType_FILE */
 #define PFSCDC_FILE_TYPE_DIR 2u  /* pfs.FileType_DIR: the path ends in '/' */
 #define PFSCDC_INFO_CHILD 1u
@@ -980,6 +984,60 @@ int pfscdc_last_source_stats(pfscdc_ctx* ctx, uint64_t out[8]);
  * sums, fill, DataRef copy; host arm: the download, the host call and the upload), out[1] depths,
  * subtree ends and sizes, out[2] the leaf hashes, out[3] the directory levels. */
 int pfscdc_last_source_timings(pfscdc_ctx* ctx, float out[4]);
+
+/* ---- DiffFile: two Sources joined by path (src/server/pfs/server/diff.go:22-96) -----------------
+ * Differ.Iterate walks sides a (the old commit; emptySource when there is none) and b (the new
+ * one) with two pointers: the side with the lesser path (Go's string order: unsigned bytes, a
+ * proper prefix first; the tag is no part of the key) is reported alone and advances; equal paths
+ * advance both sides and are reported as a pair only if the 32 hash bytes differ (equalFileInfos);
+ * then both tails are drained.  One pfscdc_diff_pair per callback, in callback order: a and b are
+ * indexes into their sides, PFSCDC_DIFF_NONE for the side the callback got nil for. */
+#define PFSCDC_DIFF_NONE 0xffffffffu
+typedef struct pfscdc_diff_pair {
+  uint32_t a, b;
+} pfscdc_diff_pair;
+
+/* The walk on the host, with no GPU call, taken literally: it does not assume sorted sides and
+ * does whatever the two pointers do.  Each side is a list with one pfscdc_file_info per entry
+ * (what pfscdc_source_host returns); a NULL or empty list is an empty side.  *out (*n pairs):
+ * pfscdc_diff_pairs_free.  PFSCDC_EINVAL: entries without infos, or a path outside the list's
+ * blob; *out is then NULL.  The specification of pfscdc_source_diff. */
+int pfscdc_diff_host(const pfscdc_index_list* a, const pfscdc_file_info* a_infos,
+                     const pfscdc_index_list* b, const pfscdc_file_info* b_infos,
+                     pfscdc_diff_pair** out, uint64_t* n);
+void pfscdc_diff_pairs_free(pfscdc_diff_pair* pairs);
+
+/* The walk over two Sources of ctx's device (a NULL a: emptySource).  The PFSCDC_DIFF knob: 1 runs
+ * the device arm.  Within a side the paths do not decrease, so the walk pairs the k-th entry of a
+ * path on side a with the k-th on side b and the longer run's surplus follows unpaired: one lane
+ * per entry finds its number in its run and the run of its path in the other side by searches,
+ * compares the hashes, and the places of the pairs follow from prefix sums of both sides' flags.
+ * 0, or a side whose paths decrease, downloads both lists and infos, calls pfscdc_diff_host and
+ * uploads the result; the two arms' arrays are identical.  Beside the pairs the diff holds, per
+ * side, the entries of that side that occur in a pair as a pfscdc_source of its own (entries in
+ * order, a fresh blob, the DataRefs packed in entry order, the infos gathered): the i-th pair
+ * with an a member is entry i of side 0's selection, and likewise b and side 1, so the paths of
+ * what changed come from the diff alone and the tar calls render only the changed files.
+ * PFSCDC_EINVAL: a NULL b, a Source of another device.  Every array the kernels fill ends in a
+ * 64-byte guard that the call checks (PFSCDC_EHIP). */
+typedef struct pfscdc_diff pfscdc_diff;
+int pfscdc_source_diff(pfscdc_ctx* ctx, const pfscdc_source* a, const pfscdc_source* b,
+                       pfscdc_diff** out);
+uint64_t pfscdc_diff_count(const pfscdc_diff* d);
+/* The pairs copied to out (pfscdc_diff_count records). */
+int pfscdc_diff_pairs(pfscdc_ctx* ctx, const pfscdc_diff* d, pfscdc_diff_pair* out);
+/* Side 0 (a) or 1 (b)'s selection, owned by the diff: pfscdc_source_list, _count and _infos take
+ * it; NULL for another side. */
+pfscdc_source* pfscdc_diff_side(pfscdc_diff* d, int side);
+int pfscdc_diff_free(pfscdc_diff* d);
+/* The last pfscdc_source_diff on ctx: out[0] 1 the device arm ran, 0 the host arm; out[1], out[2]
+ * entries of a and of b; out[3] pairs; out[4] pairs with both members; out[5] bytes copied host
+ * to device; out[6] bytes copied device to host (the accessors not counted); out[7] 0. */
+int pfscdc_last_diff_stats(pfscdc_ctx* ctx, uint64_t out[8]);
+/* Its time (ms, wall time around synchronised stages): out[0] rank and prefix sums (host arm: the
+ * download of both sides), out[1] the pairs' fill (host arm: pfscdc_diff_host), out[2] the two
+ * selections (host arm: built on the host), out[3] the guards' copy (host arm: the upload). */
+int pfscdc_last_diff_timings(pfscdc_ctx* ctx, float out[4]);
 
 /* shard (fileset/shard.go:27-49) over a merged list: cb receives each shard's path range
  * (lower, upper; "" = an open end).  A range is closed in front of the first file that finds

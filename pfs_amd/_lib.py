@@ -82,6 +82,9 @@ EXPORTED = [
     "pfscdc_source_open", "pfscdc_source_open_list", "pfscdc_source_list", "pfscdc_source_count",
     "pfscdc_source_infos", "pfscdc_source_free", "pfscdc_last_source_stats",
     "pfscdc_last_source_timings",
+    "pfscdc_diff_host", "pfscdc_diff_pairs_free", "pfscdc_source_diff", "pfscdc_diff_count",
+    "pfscdc_diff_pairs", "pfscdc_diff_side", "pfscdc_diff_free", "pfscdc_last_diff_stats",
+    "pfscdc_last_diff_timings",
 ]
 
 
@@ -150,9 +153,14 @@ class FileInfoC(C.Structure):
                 ("flags", C.c_uint32)]
 
 
-SRC_ALL, SRC_SUBTREE, SRC_LIST, SRC_GET = 0, 1, 2, 3
+SRC_ALL, SRC_SUBTREE, SRC_LIST, SRC_GET, SRC_DIFF = 0, 1, 2, 3, 4
 FILE_TYPE_FILE, FILE_TYPE_DIR = 1, 2
 INFO_CHILD = 1
+DIFF_NONE = 0xFFFFFFFF
+
+
+class DiffPairC(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32)]
 
 
 class AnnotationOut(C.Structure):
@@ -400,6 +408,16 @@ def load() -> C.CDLL:
             "pfscdc_source_free": (i32, [vp]),
             "pfscdc_last_source_stats": (i32, [vp, P(u64)]),
             "pfscdc_last_source_timings": (i32, [vp, P(C.c_float)]),
+            "pfscdc_diff_host": (i32, [vp, P(FileInfoC), vp, P(FileInfoC), P(P(DiffPairC)),
+                                       P(u64)]),
+            "pfscdc_diff_pairs_free": (None, [P(DiffPairC)]),
+            "pfscdc_source_diff": (i32, [vp, vp, vp, P(vp)]),
+            "pfscdc_diff_count": (u64, [vp]),
+            "pfscdc_diff_pairs": (i32, [vp, vp, P(DiffPairC)]),
+            "pfscdc_diff_side": (vp, [vp, i32]),
+            "pfscdc_diff_free": (i32, [vp]),
+            "pfscdc_last_diff_stats": (i32, [vp, P(u64)]),
+            "pfscdc_last_diff_timings": (i32, [vp, P(C.c_float)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

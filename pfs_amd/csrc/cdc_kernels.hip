@@ -3744,4 +3744,169 @@ hipError_t launch_src_scatter(const SrcMeta* meta, const uint64_t* base, const p
   return hipGetLastError();
 }
 
+// ---- 12. DiffFile: two Sources joined by path --------------------------------------------------
+// (server/pfs/server/diff.go:26-96 Differ.Iterate / equalFileInfos; diff.cpp takes it literally)
+//
+// Within a side the paths do not decrease (a path occurs once per tag), so the two-pointer walk is
+// a join.  For a path p with na_p entries on side a and nb_p on side b it reports the first
+// min(na_p, nb_p) entries of both sides as pairs, k-th with k-th, each only if the hashes differ,
+// and then the longer run's surplus alone; everything of a lesser path comes before.  So with
+// k = an entry's number in its run, [lb, ub) = the run of its path in the other side:
+//   an entry is paired iff k < ub - lb, with entry lb + k of the other side;
+//   an a-entry is reported if it is unpaired or its hash differs, a b-entry alone if unpaired;
+//   an a-record lies after the a-records of the a-entries before it and the b-records of the
+//   b-entries of a lesser path: exA[i] + exB[lb_b(p)] (the b-entries [lb, lb + k) are paired and
+//   report nothing of their own, and unpaired ones of p have k' >= na_p > k and follow);
+//   a b-record lies after the b-records before it and the a-records of paths <= p:
+//   exB[j] + exA[ub_a(p)].
+// 12a rank   one lane per entry of either side: one compare with its predecessor (a side whose
+//     paths decrease sets *bad, and diff_dev.cpp hands the call to the host arm), k by a search
+//     in its own side only if the predecessor's path is equal, lb and ub by searches in the other
+//     side, the 32 hash bytes; what the entry brings into its side's selection.
+// 12b scan   merge_scan_kernel as it is: side a's and side b's selections, side b's records.
+// 12c fill   one lane per entry writes its own pfscdc_diff_pair.
+// 12d select per side, one lane per selected entry: the entry, its strings and its info at its own
+//     ranges (nothing unless its counts equal them), one MrgCopy for merge_copy_kernel.
+PFS_DEV int diff_cmp_path(const RtarList& x, uint64_t i, const uint8_t* s, uint32_t n) {
+  const pfscdc_index_entry& e = x.entries[i];
+  return mrg_cmp_str((const uint8_t*)x.blob + e.path_off, e.path_len, s, n);
+}
+
+// the first entry of x[lo, hi) whose path is not below s (upper: that is above s)
+PFS_DEV uint64_t diff_bound(const RtarList& x, uint64_t lo, uint64_t hi, const uint8_t* s,
+                            uint32_t n, bool upper) {
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    const int c = diff_cmp_path(x, mid, s, n);
+    if (upper ? c <= 0 : c < 0) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kIdxBlock) void diff_rank_kernel(DiffSide a, DiffSide b,
+                                                              DiffRank* __restrict__ rank,
+                                                              MrgCount* __restrict__ sel,
+                                                              MrgCount* __restrict__ emit_b,
+                                                              uint32_t* __restrict__ bad) {
+  const uint64_t na = a.l.n, items = a.l.n + b.l.n;
+  for (uint64_t x = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; x < items;
+       x += (uint64_t)gridDim.x * kIdxBlock) {
+    const bool is_b = x >= na;
+    const DiffSide& own = is_b ? b : a;
+    const DiffSide& oth = is_b ? a : b;
+    const uint64_t i = is_b ? x - na : x;
+    const pfscdc_index_entry e = own.l.entries[i];
+    const uint8_t* s = (const uint8_t*)own.l.blob + e.path_off;
+    const uint32_t n = e.path_len;
+    uint64_t k = 0;  // its number among the entries of its path
+    if (i > 0) {
+      const int c = diff_cmp_path(own.l, i - 1, s, n);
+      if (c > 0) atomicOr(bad, 1u);
+      if (c == 0) k = i - diff_bound(own.l, 0, i, s, n, false);
+    }
+    const uint64_t lb = diff_bound(oth.l, 0, oth.l.n, s, n, false);
+    uint64_t ub = lb;
+    if (lb < oth.l.n && diff_cmp_path(oth.l, lb, s, n) == 0)
+      ub = diff_bound(oth.l, lb + 1, oth.l.n, s, n, true);
+    const bool paired = k < ub - lb;  // then lb + k < ub <= the other side's count
+    bool differ = false;
+    if (paired) {
+      const uint4* p = reinterpret_cast<const uint4*>(own.infos[i].hash);
+      const uint4* q = reinterpret_cast<const uint4*>(oth.infos[lb + k].hash);
+      const uint4 p0 = p[0], p1 = p[1], q0 = q[0], q1 = q[1];
+      differ = p0.x != q0.x || p0.y != q0.y || p0.z != q0.z || p0.w != q0.w || p1.x != q1.x ||
+               p1.y != q1.y || p1.z != q1.z || p1.w != q1.w;
+    }
+    rank[x] = DiffRank{paired ? (uint32_t)(lb + k) : PFSCDC_DIFF_NONE, (uint32_t)(is_b ? ub : lb)};
+    sel[x] = (!paired || differ)
+                 ? MrgCount{1, e.count, (uint64_t)e.path_len + e.tag_len + e.last_path_len + 3}
+                 : MrgCount{0, 0, 0};
+    if (is_b) emit_b[i] = MrgCount{paired ? 0u : 1u, 0, 0};
+  }
+}
+
+__global__ __launch_bounds__(kIdxBlock) void diff_fill_kernel(
+    uint64_t na, uint64_t nb, const DiffRank* __restrict__ rank, const MrgCount* __restrict__ sel,
+    const uint64_t* __restrict__ base_a, const MrgCount* __restrict__ emit_b,
+    const uint64_t* __restrict__ base_e, pfscdc_diff_pair* __restrict__ pairs, uint64_t npairs) {
+  for (uint64_t x = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; x < na + nb;
+       x += (uint64_t)gridDim.x * kIdxBlock) {
+    const DiffRank r = rank[x];
+    if (x < na) {
+      if (!sel[x].emit || r.other > nb) continue;
+      const uint64_t at = base_a[3 * x] + base_e[3 * (uint64_t)r.other];
+      if (at < npairs) pairs[at] = pfscdc_diff_pair{(uint32_t)x, r.partner};
+    } else {
+      const uint64_t j = x - na;
+      if (!emit_b[j].emit || r.other > na) continue;
+      const uint64_t at = base_e[3 * j] + base_a[3 * (uint64_t)r.other];
+      if (at < npairs) pairs[at] = pfscdc_diff_pair{PFSCDC_DIFF_NONE, (uint32_t)j};
+    }
+  }
+}
+
+__global__ __launch_bounds__(kIdxBlock) void diff_select_kernel(
+    DiffSide in, const MrgCount* __restrict__ sel, const uint64_t* __restrict__ base,
+    pfscdc_index_entry* __restrict__ entries, char* __restrict__ blob, MrgCopy* __restrict__ copy,
+    pfscdc_file_info* __restrict__ infos) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; i < in.l.n;
+       i += (uint64_t)gridDim.x * kIdxBlock) {
+    if (!sel[i].emit) continue;
+    const uint64_t oi = base[3 * i], first = base[3 * i + 1];
+    uint64_t at = base[3 * i + 2];
+    const pfscdc_index_entry e = in.l.entries[i];
+    if (base[3 * i + 3] - oi != 1 || base[3 * i + 4] - first != e.count ||
+        base[3 * i + 5] - at != (uint64_t)e.path_len + e.tag_len + e.last_path_len + 3)
+      continue;  // (never: the rank pass's counts)
+    const char* src = in.l.blob;
+    pfscdc_index_entry o = e;
+    o.path_off = at;
+    for (uint32_t x = 0; x < e.path_len; x++) blob[at + x] = src[e.path_off + x];
+    at += e.path_len;
+    blob[at++] = 0;
+    o.tag_off = at;
+    for (uint32_t x = 0; x < e.tag_len; x++) blob[at + x] = src[e.tag_off + x];
+    at += e.tag_len;
+    blob[at++] = 0;
+    o.last_path_off = at;
+    for (uint32_t x = 0; x < e.last_path_len; x++) blob[at + x] = src[e.last_path_off + x];
+    at += e.last_path_len;
+    blob[at] = 0;
+    o.first = (uint32_t)first;
+    entries[oi] = o;
+    if (e.count) copy[i] = MrgCopy{(uint32_t)first, e.count, e.first, 0};
+    infos[oi] = in.infos[i];
+  }
+}
+
+hipError_t launch_diff_rank(const DiffSide& a, const DiffSide& b, DiffRank* rank, MrgCount* sel,
+                            MrgCount* emit_b, uint32_t* bad, int num_cus, hipStream_t st) {
+  if (a.l.n + b.l.n == 0) return hipSuccess;
+  diff_rank_kernel<<<merge_grid(a.l.n + b.l.n, num_cus), kIdxBlock, 0, st>>>(a, b, rank, sel,
+                                                                            emit_b, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_diff_fill(uint64_t na, uint64_t nb, const DiffRank* rank, const MrgCount* sel,
+                            const uint64_t* base_a, const MrgCount* emit_b, const uint64_t* base_e,
+                            pfscdc_diff_pair* pairs, uint64_t npairs, int num_cus, hipStream_t st) {
+  if (na + nb == 0 || npairs == 0) return hipSuccess;
+  diff_fill_kernel<<<merge_grid(na + nb, num_cus), kIdxBlock, 0, st>>>(na, nb, rank, sel, base_a,
+                                                                      emit_b, base_e, pairs, npairs);
+  return hipGetLastError();
+}
+
+hipError_t launch_diff_select(const DiffSide& in, const MrgCount* sel, const uint64_t* base,
+                              pfscdc_index_entry* entries, char* blob, MrgCopy* copy,
+                              pfscdc_file_info* infos, pfscdc_full_dataref* drs, int num_cus,
+                              hipStream_t st) {
+  if (in.l.n == 0) return hipSuccess;
+  diff_select_kernel<<<merge_grid(in.l.n, num_cus), kIdxBlock, 0, st>>>(in, sel, base, entries,
+                                                                       blob, copy, infos);
+  merge_copy_kernel<<<merge_grid(in.l.n * 8, num_cus), kIdxBlock, 0, st>>>(
+      (const uint4*)in.l.drs, copy, in.l.n, (uint4*)drs);
+  return hipGetLastError();
+}
+
 }  // namespace pfscdc

@@ -20,6 +20,18 @@ struct pfscdc_dev_list {
   ~pfscdc_dev_list();
 };
 
+// A Source on the device (source_dev.cpp; a diff's selections, diff_dev.cpp): the list and one
+// pfscdc_file_info per entry of it.
+struct pfscdc_source {
+  int device = 0;
+  pfscdc_dev_list* list = nullptr;
+  void* infos = nullptr;  // pfscdc_file_info per entry of list, on the device
+  ~pfscdc_source() {
+    if (infos) (void)hipFree(infos);
+    delete list;
+  }
+};
+
 namespace pfscdc {
 
 // what pfscdc_last_resident_stats reports

@@ -173,6 +173,7 @@ struct pfscdc_ctx {
   MergeStats merge_stats;             // the last pfscdc_index_merge_ctx
   ResidentStats resident_stats;       // the last calls over device-resident lists
   SourceStats source_stats;           // the last pfscdc_source_open
+  DiffStats diff_stats;               // the last pfscdc_source_diff
 };
 
 namespace pfscdc {
@@ -181,6 +182,7 @@ IndexStats& ctx_index_stats(pfscdc_ctx* ctx) { return ctx->index_stats; }
 MergeStats& ctx_merge_stats(pfscdc_ctx* ctx) { return ctx->merge_stats; }
 ResidentStats& ctx_resident_stats(pfscdc_ctx* ctx) { return ctx->resident_stats; }
 SourceStats& ctx_source_stats(pfscdc_ctx* ctx) { return ctx->source_stats; }
+DiffStats& ctx_diff_stats(pfscdc_ctx* ctx) { return ctx->diff_stats; }
 int ctx_num_cus(const pfscdc_ctx* ctx) { return ctx->num_cus; }
 }  // namespace pfscdc
 

@@ -47,7 +47,7 @@ enum class Knob : int {
   HashBinBytes, HashWaves, HashFair, HashFairEvery,
   RefIdSplit, CommitTwoSets, CommitLongPct,
   UwWorkers, UwInflight, UwMirror, UwIndexGrouped, UwArenaPoolBytes, CtxCache, CopyThreads,
-  IndexDecode, IndexMerge, Source, Trace,
+  IndexDecode, IndexMerge, Source, Diff, Trace,
   kCount
 };
 int64_t knob(Knob k);
@@ -512,6 +512,37 @@ struct SourceStats {
   float ms[4] = {};
 };
 SourceStats& ctx_source_stats(pfscdc_ctx* ctx);
+
+// ---- DiffFile on the device (diff_dev.cpp; kernels in cdc_kernels.hip §12) ----
+struct DiffSide {  // a Source: its list and one info per entry
+  RtarList l;
+  const pfscdc_file_info* infos;
+};
+struct DiffRank {    // per entry of a side
+  uint32_t partner;  // the entry of the other side the walk meets it with, or PFSCDC_DIFF_NONE
+  uint32_t other;    // a: lower_bound of its path in b; b: upper_bound of its path in a
+};
+// One lane per entry of a (x < a.l.n) and of b: rank[x]; sel[x] = {1, DataRefs, blob bytes} if the
+// entry occurs in a pair, else zeros; emit_b[j] = {1, 0, 0} if b's entry j is reported alone;
+// *bad |= 1 (zeroed before) if a side's paths decrease: nothing else is then to be used.
+hipError_t launch_diff_rank(const DiffSide& a, const DiffSide& b, DiffRank* rank, MrgCount* sel,
+                            MrgCount* emit_b, uint32_t* bad, int num_cus, hipStream_t st);
+// after launch_merge_scan of sel[0, na) into base_a and of emit_b into base_e: pairs[0, npairs)
+hipError_t launch_diff_fill(uint64_t na, uint64_t nb, const DiffRank* rank, const MrgCount* sel,
+                            const uint64_t* base_a, const MrgCount* emit_b, const uint64_t* base_e,
+                            pfscdc_diff_pair* pairs, uint64_t npairs, int num_cus, hipStream_t st);
+// after launch_merge_scan of a side's sel into base: its selected entries, strings and infos,
+// copy[] (zeroed before) and through it their DataRefs into drs
+hipError_t launch_diff_select(const DiffSide& in, const MrgCount* sel, const uint64_t* base,
+                              pfscdc_index_entry* entries, char* blob, MrgCopy* copy,
+                              pfscdc_file_info* infos, pfscdc_full_dataref* drs, int num_cus,
+                              hipStream_t st);
+// what pfscdc_last_diff_stats / pfscdc_last_diff_timings report
+struct DiffStats {
+  uint64_t n[8] = {};
+  float ms[4] = {};
+};
+DiffStats& ctx_diff_stats(pfscdc_ctx* ctx);
 
 hipError_t launch_synth(uint8_t* out, const uint64_t* offs, uint32_t nfiles, const uint32_t* ids,
                         const uint64_t* starts, uint64_t seed, uint32_t mode, hipStream_t st);

@@ -211,6 +211,7 @@ int source_arg(int kind, const char* arg, SrcArg* out, std::string* err) {
       out->all = true;
       return PFSCDC_OK;
     case PFSCDC_SRC_SUBTREE:  // p == "/" -> p = ""
+    case PFSCDC_SRC_DIFF:     // the same filter; diffFile leaves NewErrOnEmpty out
       out->name = a == "/" ? std::string() : a;
       out->dir = out->name + "/";
       return PFSCDC_OK;
@@ -250,7 +251,8 @@ struct Item {
 bool predicate(const SrcArg& a, const std::string& path) {
   switch (a.kind) {
     case PFSCDC_SRC_ALL: return true;
-    case PFSCDC_SRC_SUBTREE: return path == a.name || has_prefix(path, a.name + "/");
+    case PFSCDC_SRC_SUBTREE:
+    case PFSCDC_SRC_DIFF: return path == a.name || has_prefix(path, a.name + "/");
     case PFSCDC_SRC_LIST:
       if (path == a.dir) return false;  // the directory itself is not listed
       if (path == a.name) return true;

@@ -15,7 +15,7 @@ namespace pfscdc {
 // A predicate with its argument cleaned (driver_file.go:173-385), in the one form all four kinds
 // share once the list is known to hold clean paths:
 //   selected(path) = all || ((path == name || HasPrefix(path, dir)) && !(exclude_dir && path == dir))
-// SUBTREE(p): name = p, dir = p + "/".  LIST(n): name = n, dir = Clean(n, true), exclude_dir.
+// SUBTREE(p) and DIFF(p): name = p, dir = p + "/" (DIFF: never NewErrOnEmpty).  LIST(n): name = n, dir = Clean(n, true), exclude_dir.
 // GET(g): name = g, dir = g + "/" (TrimRight(path, "/") == g is path == g or path == g + "/" for a
 // clean path, and the `full` filter's dir state, set at g + "/", passes HasPrefix(path, g + "/"):
 // stateless, because the inserter puts g + "/" in front of everything below it); g == "/": all.

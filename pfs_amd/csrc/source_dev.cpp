@@ -11,16 +11,6 @@
 #include "pfscdc_internal.h"
 #include "source.h"
 
-struct pfscdc_source {
-  int device = 0;
-  pfscdc_dev_list* list = nullptr;
-  void* infos = nullptr;  // pfscdc_file_info per entry of list, on the device
-  ~pfscdc_source() {
-    if (infos) (void)hipFree(infos);
-    delete list;
-  }
-};
-
 namespace {
 
 using namespace pfscdc;
@@ -49,7 +39,9 @@ RtarList view(const pfscdc_dev_list& d) {
                   (const pfscdc_full_dataref*)d.drs, d.n, d.nr, d.nb};
 }
 
-bool errs_on_empty(const SrcArg& a) {  // NewErrOnEmpty: getFile, and inspect / walk below the root
+// NewErrOnEmpty: getFile, and inspect / walk below the root; never a side of diffFile
+// (PFSCDC_SRC_DIFF), whose missing path is an empty side
+bool errs_on_empty(const SrcArg& a) {
   return a.kind == PFSCDC_SRC_GET || (a.kind == PFSCDC_SRC_SUBTREE && !a.name.empty());
 }
 

@@ -684,6 +684,110 @@ def last_source_stats(chunker) -> dict:
     return out
 
 
+def _infos_array(infos):
+    arr = (_lib.FileInfoC * max(1, len(infos)))()
+    for i, (h, size, typ, flags) in enumerate(infos):
+        arr[i] = _lib.FileInfoC((C.c_uint8 * 32)(*h), size, typ, flags)
+    return arr
+
+
+def diff_host(a: Optional[IndexList], a_infos, b: Optional[IndexList], b_infos) -> list:
+    """pfscdc_diff_host: ``Differ.Iterate``'s two-pointer walk over two sides on the host, each a
+    list with its (hash, size, type, flags) per entry as ``source_host`` returns them (None: an
+    empty side).  One ``(i, j)`` per callback, in callback order: indexes into the sides, None
+    for the side the callback got nil for."""
+    lib = _lib.load()
+    out, n = C.POINTER(_lib.DiffPairC)(), C.c_uint64()
+    rc = lib.pfscdc_diff_host(a._p if a is not None else None, _infos_array(a_infos or []),
+                              b._p if b is not None else None, _infos_array(b_infos or []),
+                              C.byref(out), C.byref(n))
+    if rc:
+        raise _lib.PfsCdcError(rc, "pfscdc_diff_host")
+    try:
+        return [(None if out[k].a == _lib.DIFF_NONE else out[k].a,
+                 None if out[k].b == _lib.DIFF_NONE else out[k].b) for k in range(n.value)]
+    finally:
+        lib.pfscdc_diff_pairs_free(out)
+
+
+class _BorrowedSource(Source):
+    """A diff's selection: owned by the diff, which it keeps alive."""
+
+    def __init__(self, ptr, device, owner):
+        super().__init__(ptr, device)
+        self._owner = owner
+
+    def free(self) -> None:
+        self._p = None
+        self._owner = None
+
+
+class Diff:
+    """An owned pfscdc_diff: the pairs ``Differ.Iterate`` reports, and per side the entries that
+    occur in them as a ``Source`` of their own (``side(0)``: the old commit's, ``side(1)``: the
+    new one's), all on the GPU."""
+
+    def __init__(self, ptr, device: int):
+        self.lib = _lib.load()
+        self._p = ptr
+        self.device = device
+
+    def __len__(self) -> int:
+        return int(self.lib.pfscdc_diff_count(self._p))
+
+    def pairs(self, chunker) -> list:
+        """``(i, j)`` per pair as ``diff_host`` gives them."""
+        n = len(self)
+        arr = (_lib.DiffPairC * max(1, n))()
+        rc = chunker.lib.pfscdc_diff_pairs(chunker.ctx, self._p, arr)
+        if rc:
+            raise _lib.PfsCdcError(rc, "pfscdc_diff_pairs")
+        return [(None if arr[k].a == _lib.DIFF_NONE else arr[k].a,
+                 None if arr[k].b == _lib.DIFF_NONE else arr[k].b) for k in range(n)]
+
+    def side(self, which: int) -> Source:
+        p = self.lib.pfscdc_diff_side(self._p, which)
+        if not p:
+            raise ValueError("a diff has sides 0 and 1")
+        return _BorrowedSource(p, self.device, self)
+
+    def free(self) -> None:
+        if self._p:
+            self.lib.pfscdc_diff_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def source_diff(chunker, a: Optional[Source], b: Source) -> Diff:
+    """pfscdc_source_diff: the walk over two Sources of ``chunker``'s device (``a`` None: the nil
+    parent commit), on the device or on the host by the PFSCDC_DIFF knob, with the same result
+    either way."""
+    out = C.c_void_p()
+    rc = chunker.lib.pfscdc_source_diff(chunker.ctx, a._p if a is not None else None,
+                                        b._p if b is not None else None, C.byref(out))
+    if rc:
+        msg = chunker.lib.pfscdc_last_error(chunker.ctx)
+        raise _lib.PfsCdcError(rc, msg.decode("utf-8", "replace") if msg else "")
+    return Diff(out, chunker.device)
+
+
+def last_diff_stats(chunker) -> dict:
+    """Counts and stage times (ms) of the last source_diff on ``chunker``'s context."""
+    n, ms = (C.c_uint64 * 8)(), (C.c_float * 4)()
+    chunker.lib.pfscdc_last_diff_stats(chunker.ctx, n)
+    chunker.lib.pfscdc_last_diff_timings(chunker.ctx, ms)
+    out = dict(zip(["device", "entries_a", "entries_b", "pairs", "both", "h2d_bytes",
+                    "d2h_bytes"], [int(x) for x in n]))
+    out.update(zip(["rank_ms", "fill_ms", "select_ms", "guards_ms"],
+                   [round(float(x), 4) for x in ms]))
+    return out
+
+
 class _SourceTarStream(_DevTarStream):
     """GetFileTAR as the reference serves it: one tar entry per entry of a source's stream,
     directories included."""
@@ -833,6 +937,40 @@ class FileSet:
         directory with everything below it) as a ``TarStream`` with one entry per entry of the
         source, directories included.  KeyError if nothing is there."""
         return _SourceTarStream(self._storage, self._source(_lib.SRC_GET, p))
+
+    def diff_file(self, old: Optional["FileSet"], path: str = "",
+                  old_path: Optional[str] = None) -> list:
+        """``diffFile``: what differs between ``old_path`` (default: ``path``) in the commit
+        ``old`` (None: the nil parent commit, an empty side) and ``path`` in this one, as
+        ``(old FileInfo or None, new FileInfo or None)`` per callback of ``Differ.Iterate``,
+        directories included.  A path one commit lacks is an empty side, not an error.  Both
+        Sources and the join stay on the GPU; only the pairs and the entries that occur in them
+        are downloaded."""
+        new_src = self._source(_lib.SRC_DIFF, path)
+        old_src = None
+        c = Chunker(ChunkParams(), self._storage.device)
+        try:
+            if old is not None:
+                old_src = old._source(_lib.SRC_DIFF, path if old_path is None else old_path)
+            d = source_diff(c, old_src, new_src)
+            try:
+                pairs = d.pairs(c)
+                sides = []
+                for which in (0, 1):
+                    s = d.side(which)
+                    sides.append([FileInfo(r["path"].decode("utf-8", "surrogateescape"),
+                                           r["tag"].decode("utf-8", "surrogateescape"), t, size, h)
+                                  for r, (h, size, t, _) in zip(s.list.download(c).raw(), s.infos(c))])
+            finally:
+                d.free()
+        finally:
+            c.close()
+            new_src.free()
+            if old_src is not None:
+                old_src.free()
+        its = [iter(sides[0]), iter(sides[1])]
+        return [(next(its[0]) if i is not None else None, next(its[1]) if j is not None else None)
+                for i, j in pairs]
 
 
 class Storage:

@@ -64,7 +64,18 @@ select, sizes, leaf hashes, the directory levels) and the whole call's wall time
 counts and bytes each way.  Every device result is compared with the host arm's, array for array
 and info for info.  Writes profiles/r12/source/source.json.
 
-usage: python tools/read_bench.py [--tar | --index | --merge | --compact | --resident | --source]
+--diff: DiffFile (pfscdc_source_diff) over two resident commits of 65,536 files of 4 KiB and of
+--files files of 256 B at fan-out 64, the new commit the old one with 1 % of the files' content
+changed, 8 files added and 8 removed: the device arm (PFSCDC_DIFF=1) and the host arm (0:
+download of both sides, pfscdc_diff_host, upload of the pairs and the selections) alternating call
+by call, with the two pfscdc_source_open calls timed beside them.  Per arm: median, min and max of
+each stage's and the whole call's wall time and of what the call leaves behind (after_ms: the
+diff's release and an upload of 16,384 entries, timed after every call so that no arm's figure
+holds the other's leftovers), the counts and the bytes each way.  The arms' pairs
+and selections are compared array for array.  Writes profiles/r7/read_path/diff.json.
+
+usage: python tools/read_bench.py [--tar | --index | --merge | --compact | --resident | --source
+                                   | --diff]
                                   [--chunks N]
                                   [--chunk-bytes B] [--files N] [--reps R] [--warmup W]
                                   [--out PATH]"""
@@ -570,11 +581,11 @@ def compact_rows(args):
     return [row]
 
 
-def source_list(n, fbytes, flat, seed):
-    """A level-0 list of n files of one DataRef of fbytes bytes each, in path order: over a
-    directory tree of fan-out 64 (/b/AA/BB/CC/fNNNNNNN, the directories the base-64 digits of N)
-    or flat (/b/fNNNNNNN).  Fixed-layout frames assembled with numpy, as synthetic_lists does."""
-    from pfs_amd import fileset as PF
+def source_frames(n, fbytes, flat, seed):
+    """The pbutil frames of n files of one DataRef of fbytes bytes each, in path order, one row
+    per file: over a directory tree of fan-out 64 (/b/AA/BB/CC/fNNNNNNN, the directories the
+    base-64 digits of N) or flat (/b/fNNNNNNN).  Fixed-layout frames assembled with numpy, as
+    synthetic_lists does.  Also the column at which a row's 32 DataRef hash bytes begin."""
     ids = np.arange(n, dtype=np.int64)
     rng = np.random.default_rng(seed)
     L = 11 if flat else 20
@@ -611,7 +622,111 @@ def source_list(n, fbytes, flat, seed):
     a[:, at + 125] = off >> 14
     assert fbytes in (256, 4096)  # size_bytes: a two-byte varint
     a[:, at + 126:at + 129] = (0x20, 0x80, fbytes >> 7)
-    return PF.index_decode_host(a.tobytes())
+    return a, at + 90
+
+
+def source_list(n, fbytes, flat, seed):
+    """The level-0 list of source_frames' files."""
+    from pfs_amd import fileset as PF
+    return PF.index_decode_host(source_frames(n, fbytes, flat, seed)[0].tobytes())
+
+
+def diff_rows(args):
+    """--diff: DiffFile over two resident commits laid out over a tree of fan-out 64: the new
+    commit is the old one with 1 % of the files' content changed, 8 files added and 8 removed.
+    pfscdc_source_diff's device arm (PFSCDC_DIFF=1) and host arm (0: download of both sides,
+    pfscdc_diff_host, upload of the pairs and the selections) alternating call by call, and the
+    two pfscdc_source_open calls beside them; the arms' pairs and selections are compared array
+    for array."""
+    import time
+
+    from pfs_amd import fileset as PF
+    rows = []
+    keys = ["rank_ms", "fill_ms", "select_ms", "guards_ms", "wall_ms", "after_ms"]
+    shapes = [(65536, 4096), (args.files, 256)] if args.files != 65536 else [(65536, 4096)]
+    for nfiles, fbytes in shapes:
+        extra = 8
+        frames, hcol = source_frames(nfiles + extra, fbytes, False, nfiles)
+        rng = np.random.default_rng(nfiles + 1)
+        old = PF.index_decode_host(frames[:nfiles].tobytes())
+        new_frames = frames.copy()
+        changed = rng.choice(nfiles, nfiles // 100, replace=False)
+        new_frames[changed, hcol] ^= 0xFF  # another DataRef hash: another content
+        keep = np.ones(nfiles + extra, dtype=bool)
+        keep[rng.choice(nfiles, extra, replace=False)] = False
+        new = PF.index_decode_host(new_frames[keep].tobytes())
+        settle = PF.index_decode_host(frames[:16384].tobytes())
+        c = Chunker(ChunkParams(), 0)
+        dev_old, dev_new = PF.DevIndexList.upload(c, old), PF.DevIndexList.upload(c, new)
+        opens = []
+        for i in range(args.warmup + args.reps):
+            t0 = time.perf_counter()
+            a = PF.source_open(c, dev_old, _lib.SRC_DIFF, "")
+            t1 = time.perf_counter()
+            b = PF.source_open(c, dev_new, _lib.SRC_DIFF, "")
+            t2 = time.perf_counter()
+            if i >= args.warmup:
+                opens.append(((t1 - t0) * 1e3, (t2 - t1) * 1e3))
+            if i + 1 < args.warmup + args.reps:
+                a.free()
+                b.free()
+        runs = {1: [], 0: []}
+        last = {}
+        for i in range(args.warmup + args.reps):
+            for arm in (1, 0):
+                _lib.set_knob("PFSCDC_DIFF", arm)
+                t0 = time.perf_counter()
+                d = PF.source_diff(c, a, b)
+                wall = (time.perf_counter() - t0) * 1e3
+                stats = PF.last_diff_stats(c)
+                if stats["device"] != arm:
+                    raise SystemExit("read_bench: the wrong arm ran")
+                if i == 0:
+                    res = [d.pairs(c)]
+                    for which in (0, 1):
+                        got = d.side(which).list.download(c)
+                        res.append((list_arrays(got), d.side(which).infos(c)))
+                        got.free()
+                    last[arm] = res
+                    if arm == 0 and last[0] != last[1]:
+                        raise SystemExit("read_bench: the device arm's diff differs from the host arm's")
+                # what a call leaves for the next one to pay: the diff's release and one call that
+                # allocates and copies (an upload of 16,384 entries), charged to the arm that ran,
+                # so that neither arm's figure holds the other's leftovers.  (The host arm's
+                # download of both sides keeps the runtime busy for some 20 ms after it returns;
+                # a call that allocates device memory right after it waits that long.)
+                t0 = time.perf_counter()
+                d.free()
+                PF.DevIndexList.upload(c, settle).free()
+                stats["after_ms"] = (time.perf_counter() - t0) * 1e3
+                if i >= args.warmup:
+                    stats["wall_ms"] = wall
+                    runs[arm].append(stats)
+        row = {"files": nfiles, "file_bytes": fbytes, "layout": "fanout64", "changed": len(changed),
+               "added": extra, "removed": extra, "reps": args.reps, "warmup": args.warmup,
+               "device_equals_host": True,
+               "stages": {"device": "rank and prefix sums, pairs, selections, guards",
+                          "host": "download, pfscdc_diff_host, selections on the host, upload"}}
+        for k, name in enumerate(("source_open_old_ms", "source_open_new_ms")):
+            x = [o[k] for o in opens]
+            row[name] = {"median": round(statistics.median(x), 3), "min": round(min(x), 3),
+                         "max": round(max(x), 3)}
+        for arm, name in ((1, "device"), (0, "host")):
+            r = runs[arm]
+            row[name] = {k: {"median": round(statistics.median(x[k] for x in r), 3),
+                             "min": round(min(x[k] for x in r), 3),
+                             "max": round(max(x[k] for x in r), 3)} for k in keys}
+            row[name].update({k: r[0][k] for k in ("entries_a", "entries_b", "pairs", "both",
+                                                   "h2d_bytes", "d2h_bytes")})
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        _lib.set_knob("PFSCDC_DIFF", _lib.knob_info()["PFSCDC_DIFF"][2])
+        a.free()
+        b.free()
+        dev_old.free()
+        dev_new.free()
+        c.close()
+    return rows
 
 
 def source_rows(args):
@@ -678,6 +793,7 @@ def main():
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--resident", action="store_true")
     ap.add_argument("--source", action="store_true")
+    ap.add_argument("--diff", action="store_true")
     ap.add_argument("--files", type=int, default=1 << 20)
     ap.add_argument("--tar", action="store_true")
     ap.add_argument("--chunks", type=int, default=1024)
@@ -709,6 +825,16 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/read_bench.py --source",
+                       "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
+            f.write("\n")
+        return
+    if args.diff:
+        if args.out == os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json"):
+            args.out = os.path.join(ROOT, "profiles", "r7", "read_path", "diff.json")
+        rows = diff_rows(args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/read_bench.py --diff",
                        "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
             f.write("\n")
         return
