@@ -1039,6 +1039,73 @@ int pfscdc_last_diff_stats(pfscdc_ctx* ctx, uint64_t out[8]);
  * selections (host arm: built on the host), out[3] the guards' copy (host arm: the upload). */
 int pfscdc_last_diff_timings(pfscdc_ctx* ctx, float out[4]);
 
+/* ---- CopyFile: a file or subtree selected and moved under a new root (src/server/pfs/server/
+ * driver_file.go:143-171 copyFile; fileset/transforms.go:20-90 NewIndexFilter, NewIndexMapper) ----
+ * in is a level-0 list (what pfscdc_index_read[_dev] or pfscdc_index_merge[_dev] returns).  With
+ * srcPath = cleanPath(src) and dstPath = cleanPath(dst) (paths.go:54-60):
+ *   1. the open's options index.WithPrefix(srcPath) and index.WithTag(src_tag), as
+ *      pfscdc_index_filter_list applies a prefix and a tag (a NULL or "" src_tag: every tag);
+ *   2. NewIndexFilter: path == srcPath || HasPrefix(path, srcPath + "/").  srcPath "/" therefore
+ *      selects nothing from a list of clean paths: PFSCDC_OK and an empty list, as in the reference;
+ *   3. NewIndexMapper: the new path is path.Join(dstPath, filepath.Rel(srcPath, path)), with Go's
+ *      Clean, Rel and Join in full: srcPath itself becomes dstPath, srcPath + "/r" becomes
+ *      dstPath + "/r" ("/r" under the root), and a path that is not clean becomes what Go makes of it.
+ * The tag, the flags, size_bytes and the DataRefs stay.  The result owns a fresh blob (the new
+ * path, the tag and an empty LastPath per entry) and the selected entries' DataRefs packed at
+ * [first, first + count) in entry order: the tar calls and pfscdc_dev_list_upload take it as it
+ * is.  PFSCDC_EINVAL, with *out NULL: an entry with a Range, strings or DataRefs outside the
+ * list's arrays, a new path longer than 2^32 - 1 bytes.  The specification of
+ * pfscdc_dev_list_copy_map, with no GPU call. */
+int pfscdc_copy_map_host(const pfscdc_index_list* in, const char* src, const char* src_tag,
+                         const char* dst, pfscdc_index_list** out);
+/* The same over a resident list on ctx; *out: pfscdc_dev_list_free.  The PFSCDC_COPY_MAP knob: 1
+ * runs the device arm (one lane per entry checks its bounds and its order against its
+ * predecessor, evaluates the tag test and the predicate and counts what it emits; prefix sums; a
+ * fill that writes dstPath and the path's tail at the entry's own ranges; the DataRef copy), 0
+ * downloads the list, calls pfscdc_copy_map_host and uploads its result; the arrays are identical.
+ * The device arm hands a call to the host arm for a list that is not in (path, tag) order, holds
+ * an entry with a Range, or selects a path that is not clean as a file path (IsClean(p, false));
+ * pfscdc_last_copy_map_stats says which ran.  Errors as pfscdc_copy_map_host's (texts:
+ * pfscdc_last_error).  Every array the kernels fill ends in a 64-byte guard that the call checks
+ * (PFSCDC_EHIP). */
+int pfscdc_dev_list_copy_map(pfscdc_ctx* ctx, const pfscdc_dev_list* in, const char* src,
+                             const char* src_tag, const char* dst, pfscdc_dev_list** out);
+/* The same over a host list, which is uploaded first (NULL: an empty list). */
+int pfscdc_copy_map_list(pfscdc_ctx* ctx, const pfscdc_index_list* in, const char* src,
+                         const char* src_tag, const char* dst, pfscdc_dev_list** out);
+/* The last of the two calls above on ctx: out[0] 1 the device arm ran, 0 the host arm; out[1]
+ * entries in; out[2] entries out; out[3] DataRefs out; out[4] blob bytes out; out[5] bytes copied
+ * host to device; out[6] bytes copied device to host; out[7] 0. */
+int pfscdc_last_copy_map_stats(pfscdc_ctx* ctx, uint64_t out[8]);
+/* Its time (ms, wall time around synchronised stages): out[0] count and prefix sums, out[1] the
+ * fill, out[2] the DataRef copy, out[3] the guards' copy (host arm: the download, the host call,
+ * the upload, 0). */
+int pfscdc_last_copy_map_timings(pfscdc_ctx* ctx, float out[4]);
+
+/* UnorderedWriter.Copy (fileset/unordered_writer.go:151-168): the buffer is serialized, then one
+ * more fileset is written (withWriter): for every entry of files in order Delete(path, tag)
+ * unless append_file, then Copy(entry, tag) as pfscdc_fsw_copy, in prefetch runs as
+ * pfscdc_fsw_copy_lists forms them.  tag (NULL or "": "default") replaces the entries' tags.
+ * The fileset takes the next number after everything serialized so far, and its events follow
+ * all earlier filesets' events: what is pending is written and every group writer is joined
+ * first, with any PFSCDC_UW_WORKERS.  An empty (or NULL) list still yields a fileset, with no
+ * roots.  A later directory Delete sees the copied files.  Sticky errors, named by
+ * pfscdc_uw_last_error: PFSCDC_ESTATE without a store (pfscdc_uw_set_store) or after Close;
+ * PFSCDC_EINVAL (checkPath, the path named) for two entries that come to one (path, tag), as two
+ * source tags of one path do, and for a list that is not in path order; PFSCDC_ENOTFOUND /
+ * PFSCDC_ECORRUPT from the reads of the chunks that are re-rolled. */
+int pfscdc_uw_copy(pfscdc_uwriter* w, const pfscdc_index_list* files, const char* tag,
+                   int append_file);
+/* driver.copyFile (driver_file.go:143-171) in one call: Storage.Open(filesets,
+ * WithPrefix(cleanPath(src)), WithTag(src_tag)) as pfscdc_fsw_copy_filesets opens them (both roots
+ * of every fileset read with the filter, then merged as PFSCDC_MERGE_FILES; one fileset is read
+ * with no merge) on a cached context that is not the data ctx, the selection and path transform
+ * (PFSCDC_COPY_MAP at 1: pfscdc_copy_map_list and a download; at 0: pfscdc_copy_map_host on the
+ * opened list), and pfscdc_uw_copy.  n == 0 copies an empty list. */
+int pfscdc_uw_copy_file(pfscdc_uwriter* w, const pfscdc_fileset_info* filesets, uint32_t n,
+                        const char* src, const char* src_tag, const char* dst, const char* tag,
+                        int append_file);
+
 /* shard (fileset/shard.go:27-49) over a merged list: cb receives each shard's path range
  * (lower, upper; "" = an open end).  A range is closed in front of the first file that finds
  * threshold or more content bytes collected (the test comes before the file is added); its upper

@@ -85,6 +85,9 @@ EXPORTED = [
     "pfscdc_diff_host", "pfscdc_diff_pairs_free", "pfscdc_source_diff", "pfscdc_diff_count",
     "pfscdc_diff_pairs", "pfscdc_diff_side", "pfscdc_diff_free", "pfscdc_last_diff_stats",
     "pfscdc_last_diff_timings",
+    "pfscdc_copy_map_host", "pfscdc_dev_list_copy_map", "pfscdc_copy_map_list",
+    "pfscdc_last_copy_map_stats", "pfscdc_last_copy_map_timings", "pfscdc_uw_copy",
+    "pfscdc_uw_copy_file",
 ]
 
 
@@ -418,6 +421,14 @@ def load() -> C.CDLL:
             "pfscdc_diff_free": (i32, [vp]),
             "pfscdc_last_diff_stats": (i32, [vp, P(u64)]),
             "pfscdc_last_diff_timings": (i32, [vp, P(C.c_float)]),
+            "pfscdc_copy_map_host": (i32, [vp, C.c_char_p, C.c_char_p, C.c_char_p, P(vp)]),
+            "pfscdc_dev_list_copy_map": (i32, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, P(vp)]),
+            "pfscdc_copy_map_list": (i32, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, P(vp)]),
+            "pfscdc_last_copy_map_stats": (i32, [vp, P(u64)]),
+            "pfscdc_last_copy_map_timings": (i32, [vp, P(C.c_float)]),
+            "pfscdc_uw_copy": (i32, [vp, vp, C.c_char_p, i32]),
+            "pfscdc_uw_copy_file": (i32, [vp, P(FilesetInfo), u32, C.c_char_p, C.c_char_p,
+                                          C.c_char_p, C.c_char_p, i32]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

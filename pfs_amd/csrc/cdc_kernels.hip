@@ -3909,4 +3909,158 @@ hipError_t launch_diff_select(const DiffSide& in, const MrgCount* sel, const uin
   return hipGetLastError();
 }
 
+// ---- 13. CopyFile: a subtree selected and moved under a new root -------------------------------
+// (server/pfs/server/driver_file.go:143-171 copyFile, fileset/transforms.go:20-90 NewIndexFilter /
+// NewIndexMapper, index/reader.go:95-122 atStart / atEnd; copy_map.cpp takes them literally)
+//
+// The open's options keep the entries from the first atStart (path >= srcPath) to the first atEnd
+// (the path's first min(len) bytes above srcPath's) whose tag passes; the filter then keeps
+// path == srcPath || HasPrefix(path, srcPath + "/"); the mapper rewrites the path to
+// Join(dstPath, Rel(srcPath, path)).  Two facts let one lane decide its entry alone:
+//  (1) For a list in (path, tag) order both atStart and atEnd are monotone along the list (a path
+//      at or above srcPath stays so, and once a path's leading bytes exceed srcPath's every later
+//      path's do), so the entries between them are those with path >= srcPath and !atEnd(path),
+//      which is HasPrefix(path, srcPath) for a non-empty srcPath: a shorter path is below srcPath
+//      or past it.  The filter's predicate implies that test, so the selection is the predicate
+//      and the tag test, entry by entry.
+//  (2) For a selected path that is clean as a file path (IsClean(p, false): rooted, no empty, "."
+//      or ".." component, no trailing '/'), Clean(path) = path, so Rel(srcPath, path) is "." for
+//      path == srcPath and else the bytes after srcPath + "/", and Join gives dstPath, or
+//      dstPath + "/" + tail ("/" + tail under the root).  The selected paths share the prefix
+//      srcPath, which is replaced whole, so the output keeps the input's (path, tag) order.
+// A list out of order, or a selected path that is not clean, sets a bit in *bad and
+// copy_map_dev.cpp hands the call to the host arm, which does what the reference does.
+// 13a count  one lane per input entry: its bounds before any byte of the blob is read, the order
+//     against its predecessor, the tag test and the predicate, cleanliness if selected:
+//     {1, DataRefs, new path + tag + empty LastPath + three NULs}.
+// 13b scan   merge_scan_kernel as it is.
+// 13c fill   one lane per selected entry writes the entry, dstPath and the path's tail, the tag
+//     (nothing unless its counts equal its ranges), one MrgCopy for merge_copy_kernel.
+struct CmapItem {
+  MrgCount c;
+  uint32_t keep;  // the path's bytes [n - keep, n) follow the new root
+  uint32_t root;  // the new root's bytes: dst_len, or 0 for a tail under "/"
+};
+
+PFS_DEV CmapItem cmap_item(const RtarList& in, const CmapPred& pr, uint64_t i, uint32_t* bad) {
+  CmapItem it{MrgCount{0, 0, 0}, 0, 0};
+  const pfscdc_index_entry e = in.entries[i];
+  if (!src_entry_ok(in, e)) {
+    *bad |= kSrcMalformed;
+    return it;
+  }
+  if (e.flags & (PFSCDC_IDX_HAS_RANGE | PFSCDC_IDX_HAS_CHUNK_REF)) *bad |= kSrcNotLevel0;
+  const uint8_t* s = (const uint8_t*)in.blob + e.path_off;
+  const uint8_t* t = (const uint8_t*)in.blob + e.tag_off;
+  const uint32_t n = e.path_len;
+  if (i > 0) {
+    const pfscdc_index_entry q = in.entries[i - 1];
+    if (!src_entry_ok(in, q)) {
+      *bad |= kSrcMalformed;
+      return it;
+    }
+    int cmp = mrg_cmp_str((const uint8_t*)in.blob + q.path_off, q.path_len, s, n);
+    if (cmp == 0) cmp = mrg_cmp_str((const uint8_t*)in.blob + q.tag_off, q.tag_len, t, e.tag_len);
+    if (cmp > 0) *bad |= kSrcUnordered;
+  }
+  if (pr.tag_len) {  // index.WithTag
+    bool eq = e.tag_len == pr.tag_len;
+    for (uint32_t k = 0; eq && k < pr.tag_len; k++) eq = t[k] == (uint8_t)pr.tag[k];
+    if (!eq) return it;
+  }
+  // path == srcPath || HasPrefix(path, srcPath + "/")
+  if (n < pr.src_len) return it;
+  for (uint32_t k = 0; k < pr.src_len; k++)
+    if (s[k] != (uint8_t)pr.src[k]) return it;
+  if (n > pr.src_len && s[pr.src_len] != '/') return it;
+  // IsClean(p, false)
+  bool clean = n > 0 && s[0] == '/';
+  for (uint32_t k = 1, start = 1; clean && k <= n; k++) {
+    if (k < n && s[k] != '/') continue;
+    const uint32_t cl = k - start;
+    if (cl == 0) clean = false;
+    else if (cl == 1) clean = s[start] != '.';
+    else if (cl == 2) clean = s[start] != '.' || s[start + 1] != '.';
+    start = k + 1;
+  }
+  it.keep = n - pr.src_len;
+  it.root = (it.keep && pr.dst_len == 1) ? 0 : pr.dst_len;  // dstPath "/" + "/tail" is "/tail"
+  const uint64_t len = (uint64_t)it.root + it.keep;
+  if (!clean || len > 0xffffffffull) *bad |= kSrcUnclean;
+  it.c = MrgCount{1, e.count, len + e.tag_len + 3};
+  return it;
+}
+
+__global__ __launch_bounds__(kIdxBlock) void cmap_count_kernel(RtarList in, CmapPred pr,
+                                                               MrgCount* __restrict__ cnt,
+                                                               uint32_t* __restrict__ bad) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; i < in.n;
+       i += (uint64_t)gridDim.x * kIdxBlock) {
+    uint32_t b = 0;
+    cnt[i] = cmap_item(in, pr, i, &b).c;
+    if (b) atomicOr(bad, b);
+  }
+}
+
+__global__ __launch_bounds__(kIdxBlock) void cmap_fill_kernel(
+    RtarList in, CmapPred pr, const MrgCount* __restrict__ cnt, const uint64_t* __restrict__ base,
+    pfscdc_index_entry* __restrict__ entries, char* __restrict__ blob, MrgCopy* __restrict__ copy) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; i < in.n;
+       i += (uint64_t)gridDim.x * kIdxBlock) {
+    if (!cnt[i].emit) continue;
+    const uint64_t oi = base[3 * i], first = base[3 * i + 1];
+    uint64_t at = base[3 * i + 2];
+    uint32_t b = 0;
+    const CmapItem it = cmap_item(in, pr, i, &b);
+    if (b || base[3 * i + 3] - oi != 1 || base[3 * i + 4] - first != it.c.recs ||
+        base[3 * i + 5] - at != it.c.blob)
+      continue;  // (never: the count pass's walk)
+    const pfscdc_index_entry e = in.entries[i];
+    const char* src = in.blob;
+    pfscdc_index_entry o = e;
+    o.path_off = at;
+    o.path_len = it.root + it.keep;
+    for (uint32_t x = 0; x < it.root; x++) blob[at + x] = pr.dst[x];
+    at += it.root;
+    const uint64_t tail = e.path_off + (e.path_len - it.keep);
+    for (uint32_t x = 0; x < it.keep; x++) blob[at + x] = src[tail + x];
+    at += it.keep;
+    blob[at++] = 0;
+    o.tag_off = at;
+    for (uint32_t x = 0; x < e.tag_len; x++) blob[at + x] = src[e.tag_off + x];
+    at += e.tag_len;
+    blob[at++] = 0;
+    o.last_path_off = at;
+    o.last_path_len = 0;
+    blob[at] = 0;
+    o.first = (uint32_t)first;
+    entries[oi] = o;
+    if (e.count) copy[i] = MrgCopy{(uint32_t)first, e.count, e.first, 0};
+  }
+}
+
+hipError_t launch_cmap_count(const RtarList& in, const CmapPred& pr, MrgCount* cnt, uint32_t* bad,
+                             int num_cus, hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  cmap_count_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(in, pr, cnt, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmap_fill(const RtarList& in, const CmapPred& pr, const MrgCount* cnt,
+                            const uint64_t* base, pfscdc_index_entry* entries, char* blob,
+                            MrgCopy* copy, int num_cus, hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  cmap_fill_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(in, pr, cnt, base, entries,
+                                                                   blob, copy);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmap_copy(const RtarList& in, const MrgCopy* copy, pfscdc_full_dataref* drs,
+                            int num_cus, hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  merge_copy_kernel<<<merge_grid(in.n * 8, num_cus), kIdxBlock, 0, st>>>(
+      (const uint4*)in.drs, copy, in.n, (uint4*)drs);
+  return hipGetLastError();
+}
+
 }  // namespace pfscdc

@@ -28,6 +28,7 @@
 #include <thread>
 #include <vector>
 
+#include "copy_map.h"
 #include "pfscdc_internal.h"
 
 namespace {
@@ -825,6 +826,16 @@ struct pfscdc_uwriter {  // unordered_writer.go:15-26
     }
     for (auto& a : pool)
       if (a->pinned) arena_pool().give(std::move(a));
+    ctx_cache().give(read_ctx);
+  }
+  pfscdc_ctx* read_ctx = nullptr;  // CopyFile's index reads, merge and map: not a data ctx
+  pfscdc_ctx* reader() {
+    if (!read_ctx) {
+      pfscdc_params p;
+      pfscdc_default_params(&p);
+      read_ctx = ctx_cache().take(p, workers[0]->device, 0);
+    }
+    return read_ctx;
   }
   double put_copy_ms = 0;  // host copies of the Puts into the arenas
   bool mirror = true;  // the PFSCDC_UW_MIRROR knob (0: upload at group write time instead)
@@ -1331,8 +1342,12 @@ namespace {
 // the plaintext the chunk writer keeps: it is dropped after the run.
 constexpr uint64_t kCopyRunBytes = 256ull << 20;
 
-int fsw_copy_list(pfscdc_fswriter* w, const pfscdc_index_list* l) {
-  pfscdc_writer* cw = w->fw->cw;
+// Every entry of l as a Copy into fw, in prefetch runs.  tag (not NULL) replaces the entries'
+// tags; del_first puts Delete(path, tag) in front of every Copy (UnorderedWriter.Copy without
+// appendFile).  *what names the step that failed.
+int copy_list_runs(FilesetWriter* fw, const pfscdc_index_list* l, const char* tag, bool del_first,
+                   std::string* what) {
+  pfscdc_writer* cw = fw->cw;
   const uint32_t n = pfscdc_index_list_count(l);
   const pfscdc_index_entry* e = pfscdc_index_list_entries(l);
   const char* blob = pfscdc_index_list_blob(l, nullptr);
@@ -1349,19 +1364,169 @@ int fsw_copy_list(pfscdc_fswriter* w, const pfscdc_index_list* l) {
           held += (uint64_t)drs[k].ref_size;
     const uint32_t first = e[i].first, last = e[j - 1].first + e[j - 1].count;
     int rc = held ? pfscdc_writer_prefetch(cw, drs + first, last - first) : PFSCDC_OK;
-    if (rc) return w->fail(rc, "Copy (prefetch)");
+    if (rc) {
+      *what = "Copy (prefetch)";
+      return rc;
+    }
     for (; i < j; i++) {
-      rc = w->fw->copy(blob + e[i].path_off, blob + e[i].tag_off, drs + e[i].first, e[i].count);
-      if (rc) return w->fail(rc, std::string("Copy ") + (blob + e[i].path_off));
+      const char* path = blob + e[i].path_off;
+      const char* t = tag ? tag : blob + e[i].tag_off;
+      if (del_first && (rc = fw->del(path, t))) {
+        *what = std::string("Delete ") + path;
+        return rc;
+      }
+      rc = fw->copy(path, t, drs + e[i].first, e[i].count);
+      if (rc) {
+        *what = std::string("Copy ") + path;
+        return rc;
+      }
     }
     pfscdc::writer_drop_prefetched(cw);
   }
   return PFSCDC_OK;
 }
 
+int fsw_copy_list(pfscdc_fswriter* w, const pfscdc_index_list* l) {
+  std::string what;
+  const int rc = copy_list_runs(w->fw.get(), l, nullptr, false, &what);
+  return rc ? w->fail(rc, what) : PFSCDC_OK;
+}
+
+struct FreeList {
+  void operator()(pfscdc_index_list* l) const { pfscdc_index_list_free(l); }
+};
+using OwnedList = std::unique_ptr<pfscdc_index_list, FreeList>;
+
+// Storage.Open(ids, opts...) (storage.go:111-128): both roots of every fileset through the index
+// reader with the filter, then merged; one fileset is read with no merge.  *files / *deletes
+// point at the opened lists (NULL for none), which o keeps alive.
+struct Opened {
+  std::vector<OwnedList> lists;  // fileset k: its deletive list, then its additive
+  OwnedList merged_files, merged_deletes;
+  const pfscdc_index_list *files = nullptr, *deletes = nullptr;
+};
+int open_filesets(pfscdc_ctx* ctx, const pfscdc_store* store, const pfscdc_fileset_info* filesets,
+                  uint32_t n, const pfscdc_index_filter* filter, bool want_deletes, Opened* o,
+                  std::string* what) {
+  o->lists.resize(2 * (size_t)n);
+  std::vector<const pfscdc_index_list*> all(2 * (size_t)n), dele(n);
+  for (uint32_t k = 0; k < n; k++)
+    for (int which = 0; which < 2; which++) {
+      const pfscdc_fileset_info& f = filesets[k];
+      pfscdc_index_list* l = nullptr;
+      const int rc = pfscdc_index_read(ctx, store, which ? f.additive_root : f.deletive_root,
+                                       which ? f.additive_root_len : f.deletive_root_len, filter, &l);
+      if (rc) {
+        *what = std::string("Open: ") + pfscdc_last_error(ctx);
+        return rc;
+      }
+      o->lists[2 * k + which].reset(l);
+      all[2 * k + which] = l;
+      if (!which) dele[k] = l;
+    }
+  if (n == 0) return PFSCDC_OK;
+  if (n == 1) {  // one fileset is read with no merge
+    o->files = all[1];
+    o->deletes = all[0];
+    return PFSCDC_OK;
+  }
+  pfscdc_index_list *files = nullptr, *deletes = nullptr;
+  int rc = PFSCDC_OK;
+  if (want_deletes) rc = pfscdc_index_merge_ctx(ctx, PFSCDC_MERGE_DELETIVE, dele.data(), n, &deletes);
+  o->merged_deletes.reset(deletes);
+  if (!rc) rc = pfscdc_index_merge_ctx(ctx, PFSCDC_MERGE_FILES, all.data(), n, &files);
+  o->merged_files.reset(files);
+  if (rc) {
+    *what = std::string("merge: ") + pfscdc_last_error(ctx);
+    return rc;
+  }
+  o->files = files;
+  o->deletes = deletes;
+  return PFSCDC_OK;
+}
+
+// UnorderedWriter.Copy (unordered_writer.go:151-168): serialize, then one fileset written by
+// withWriter, every file of fs as Delete (unless appendFile) and Copy under tag.  Serialized
+// filesets are numbered in order and their events go out in that order, so everything pending
+// is written and every group writer joined first; no events are held after that, and the
+// copy's go straight out under emit_mu.  It runs on the first group writer's streams.
+int uw_copy(pfscdc_uwriter* w, const pfscdc_index_list* files, std::string tag, bool append) {
+  if (!w->store) return w->fail(PFSCDC_ESTATE, "Copy without a store");
+  w->started = true;
+  int rc = w->serialize();
+  if (!rc) rc = w->flush_pending(false);
+  const int jr = w->join();
+  if (!rc) rc = jr;
+  if (rc) return w->fail(rc, "Copy (the filesets before it)");
+  if (tag.empty()) tag = "default";
+  Streams& st = w->workers[0]->st;
+  st.hold = nullptr;
+  const uint32_t fs = w->next_fileset++;
+  FilesetWriter fw(&st, fs);
+  std::string what = "Copy";
+  rc = fw.open();
+  if (!rc) rc = copy_list_runs(&fw, files, tag.c_str(), !append, &what);
+  if (!rc) {
+    what = "Copy (Close)";
+    rc = fw.close();
+  }
+  w->mem_available = w->mem_threshold;  // withWriter resets the buffer's budget
+  // the number is spent either way, as a failed group's are
+  w->keys.emplace_back(fw.info.files, fw.info.deletes);
+  {
+    std::lock_guard<std::mutex> lk(w->fs_mu);
+    if (w->filesets.size() <= fs) w->filesets.resize((size_t)fs + 1);
+    if (!rc) w->filesets[fs] = std::move(fw.info);
+  }
+  return rc ? w->fail(rc, what.c_str()) : PFSCDC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pfscdc_uw_copy(pfscdc_uwriter* w, const pfscdc_index_list* files, const char* tag,
+                   int append_file) {
+  if (!w) return PFSCDC_EINVAL;
+  if (w->err) return w->err;
+  if (w->closed) return w->fail(PFSCDC_ESTATE, "Copy after Close");
+  return uw_copy(w, files, tag ? tag : "", append_file != 0);
+}
+
+int pfscdc_uw_copy_file(pfscdc_uwriter* w, const pfscdc_fileset_info* filesets, uint32_t n,
+                        const char* src, const char* src_tag, const char* dst, const char* tag,
+                        int append_file) {
+  if (!w || (n && !filesets)) return PFSCDC_EINVAL;
+  if (w->err) return w->err;
+  if (w->closed) return w->fail(PFSCDC_ESTATE, "CopyFile after Close");
+  if (!w->store) return w->fail(PFSCDC_ESTATE, "CopyFile without a store");
+  pfscdc_ctx* ctx = w->reader();
+  if (!ctx) return w->fail(PFSCDC_EHIP, "CopyFile: no context for the index reads");
+  // openCommit(srcCommit, index.WithPrefix(srcPath), index.WithTag(src.Tag))
+  const pfscdc::CopyArg a = pfscdc::copy_arg(src, src_tag, dst);
+  const pfscdc_index_filter filter{nullptr, nullptr, a.src.c_str(),
+                                   a.tag.empty() ? nullptr : a.tag.c_str()};
+  Opened o;
+  std::string what;
+  if (int rc = open_filesets(ctx, w->store, filesets, n, &filter, false, &o, &what))
+    return w->fail(rc, ("CopyFile " + what).c_str());
+  // NewIndexFilter and NewIndexMapper: on the device by the PFSCDC_COPY_MAP knob, else on the
+  // host list as it is (the host arm's download and upload would only move it there and back)
+  pfscdc_index_list* mapped = nullptr;
+  int rc = PFSCDC_OK;
+  if (pfscdc::knob(pfscdc::Knob::CopyMap) == 0) {
+    rc = pfscdc_copy_map_host(o.files, src, src_tag, dst, &mapped);
+    if (rc) return w->fail(rc, "CopyFile: the source list is not a level-0 list");
+  } else {
+    pfscdc_dev_list* dev = nullptr;
+    rc = pfscdc_copy_map_list(ctx, o.files, src, src_tag, dst, &dev);
+    if (!rc) rc = pfscdc_dev_list_download(ctx, dev, &mapped);
+    pfscdc_dev_list_free(dev);
+    if (rc) return w->fail(rc, (std::string("CopyFile: ") + pfscdc_last_error(ctx)).c_str());
+  }
+  OwnedList own(mapped);
+  return uw_copy(w, mapped, tag ? tag : "", append_file != 0);
+}
 
 int pfscdc_fsw_create(pfscdc_ctx* data_ctx, const pfscdc_params* index_params, pfscdc_store* store,
                       pfscdc_uw_cb cb, void* user, pfscdc_fswriter** out) {
@@ -1419,35 +1584,13 @@ int pfscdc_fsw_copy_filesets(pfscdc_fswriter* w, const pfscdc_fileset_info* file
   if (w->err) return w->err;
   if (w->closed) return w->fail(PFSCDC_ESTATE, "CopyFiles after Close");
   if (n == 0) return PFSCDC_OK;  // Storage.Open: emptyFileSet
-  // Storage.Open(ids, opts...): both roots of every fileset through the index reader
-  struct Free {
-    void operator()(pfscdc_index_list* l) const { pfscdc_index_list_free(l); }
-  };
-  using Owned = std::unique_ptr<pfscdc_index_list, Free>;
   pfscdc_ctx* ctx = w->reader();
   if (!ctx) return w->fail(PFSCDC_EHIP, "Open: no context for the index reads");
-  std::vector<Owned> lists(2 * (size_t)n);  // fileset k: its deletive list, then its additive
-  std::vector<const pfscdc_index_list*> all(2 * (size_t)n), dele(n);
-  for (uint32_t k = 0; k < n; k++)
-    for (int which = 0; which < 2; which++) {
-      const pfscdc_fileset_info& f = filesets[k];
-      pfscdc_index_list* l = nullptr;
-      const int rc = pfscdc_index_read(ctx, w->store, which ? f.additive_root : f.deletive_root,
-                                       which ? f.additive_root_len : f.deletive_root_len, filter, &l);
-      if (rc) return w->fail(rc, std::string("Open: ") + pfscdc_last_error(ctx));
-      lists[2 * k + which].reset(l);
-      all[2 * k + which] = l;
-      if (!which) dele[k] = l;
-    }
-  if (n == 1)  // one fileset is read with no merge
-    return pfscdc_fsw_copy_lists(w, all[1], all[0]);
-  pfscdc_index_list *files = nullptr, *deletes = nullptr;
-  int rc = pfscdc_index_merge_ctx(ctx, PFSCDC_MERGE_DELETIVE, dele.data(), n, &deletes);
-  Owned own_d(deletes);
-  if (!rc) rc = pfscdc_index_merge_ctx(ctx, PFSCDC_MERGE_FILES, all.data(), n, &files);
-  Owned own_f(files);
-  if (rc) return w->fail(rc, std::string("merge: ") + pfscdc_last_error(ctx));
-  return pfscdc_fsw_copy_lists(w, files, deletes);
+  Opened o;
+  std::string what;
+  if (int rc = open_filesets(ctx, w->store, filesets, n, filter, true, &o, &what))
+    return w->fail(rc, what);
+  return pfscdc_fsw_copy_lists(w, o.files, o.deletes);
 }
 
 int pfscdc_fsw_close(pfscdc_fswriter* w) {

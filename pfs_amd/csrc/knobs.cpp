@@ -50,6 +50,7 @@ constexpr KnobDef kDefs[(int)Knob::kCount] = {
     {"PFSCDC_INDEX_MERGE", 0, 0, 1},        // index merge with a ctx: 1 device, 0 host
     {"PFSCDC_SOURCE", 1, 0, 1},             // the Source with a ctx: 1 device, 0 host
     {"PFSCDC_DIFF", 1, 0, 1},               // DiffFile over two Sources: 1 device, 0 host
+    {"PFSCDC_COPY_MAP", 1, 0, 1},           // CopyFile's selection and transform: 1 device, 0 host
     {"PFSCDC_TRACE", 0, 0, 1},              // stage timelines on stderr
 };
 

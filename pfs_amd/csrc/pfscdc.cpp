@@ -174,6 +174,7 @@ struct pfscdc_ctx {
   ResidentStats resident_stats;       // the last calls over device-resident lists
   SourceStats source_stats;           // the last pfscdc_source_open
   DiffStats diff_stats;               // the last pfscdc_source_diff
+  CopyMapStats copy_map_stats;        // the last pfscdc_dev_list_copy_map
 };
 
 namespace pfscdc {
@@ -183,6 +184,7 @@ MergeStats& ctx_merge_stats(pfscdc_ctx* ctx) { return ctx->merge_stats; }
 ResidentStats& ctx_resident_stats(pfscdc_ctx* ctx) { return ctx->resident_stats; }
 SourceStats& ctx_source_stats(pfscdc_ctx* ctx) { return ctx->source_stats; }
 DiffStats& ctx_diff_stats(pfscdc_ctx* ctx) { return ctx->diff_stats; }
+CopyMapStats& ctx_copy_map_stats(pfscdc_ctx* ctx) { return ctx->copy_map_stats; }
 int ctx_num_cus(const pfscdc_ctx* ctx) { return ctx->num_cus; }
 }  // namespace pfscdc
 

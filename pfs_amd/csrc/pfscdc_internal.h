@@ -47,7 +47,7 @@ enum class Knob : int {
   HashBinBytes, HashWaves, HashFair, HashFairEvery,
   RefIdSplit, CommitTwoSets, CommitLongPct,
   UwWorkers, UwInflight, UwMirror, UwIndexGrouped, UwArenaPoolBytes, CtxCache, CopyThreads,
-  IndexDecode, IndexMerge, Source, Diff, Trace,
+  IndexDecode, IndexMerge, Source, Diff, CopyMap, Trace,
   kCount
 };
 int64_t knob(Knob k);
@@ -543,6 +543,31 @@ struct DiffStats {
   float ms[4] = {};
 };
 DiffStats& ctx_diff_stats(pfscdc_ctx* ctx);
+
+// ---- CopyFile's selection and path transform (copy_map_dev.cpp; kernels in cdc_kernels.hip §13) ----
+struct CmapPred {  // CopyArg (copy_map.h) with its strings on the device
+  const char *src, *dst, *tag;  // cleanPath(src), cleanPath(dst), the source tag ("": every tag)
+  uint32_t src_len, dst_len, tag_len, reserved;
+};
+// cnt[i] = {1, DataRefs, blob bytes} if input entry i is selected, else zeros; *bad |= SrcBad
+// (zeroed before): kSrcMalformed, kSrcNotLevel0, kSrcUnordered, and kSrcUnclean for a selected
+// path that is not IsClean(p, false) or whose new path exceeds 2^32 - 1 bytes
+hipError_t launch_cmap_count(const RtarList& in, const CmapPred& pr, MrgCount* cnt, uint32_t* bad,
+                             int num_cus, hipStream_t st);
+// after launch_merge_scan of cnt into base: the selected entries with their new paths and tags,
+// and copy[] (zeroed before) for launch_cmap_copy
+hipError_t launch_cmap_fill(const RtarList& in, const CmapPred& pr, const MrgCount* cnt,
+                            const uint64_t* base, pfscdc_index_entry* entries, char* blob,
+                            MrgCopy* copy, int num_cus, hipStream_t st);
+// the DataRefs copy[] names (merge_copy_kernel over a single list)
+hipError_t launch_cmap_copy(const RtarList& in, const MrgCopy* copy, pfscdc_full_dataref* drs,
+                            int num_cus, hipStream_t st);
+// what pfscdc_last_copy_map_stats / pfscdc_last_copy_map_timings report
+struct CopyMapStats {
+  uint64_t n[8] = {};
+  float ms[4] = {};
+};
+CopyMapStats& ctx_copy_map_stats(pfscdc_ctx* ctx);
 
 hipError_t launch_synth(uint8_t* out, const uint64_t* offs, uint32_t nfiles, const uint32_t* ids,
                         const uint64_t* starts, uint64_t seed, uint32_t mode, hipStream_t st);

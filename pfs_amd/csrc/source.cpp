@@ -113,49 +113,8 @@ void Blake2b256::sum(uint8_t out[32]) {
     for (int b = 0; b < 8; b++) out[8 * i + b] = (uint8_t)(h[i] >> (8 * b));
 }
 
-// ---- Go's path.Clean, path.Dir, strings.Trim*; fileset.Clean; cleanPath ----
+// ---- Go's path.Dir; fileset.Clean (path.Clean, strings.Trim* and cleanPath: paths.h) ----
 namespace {
-
-std::string go_clean(const std::string& p) {  // path.Clean
-  if (p.empty()) return ".";
-  const bool rooted = p[0] == '/';
-  const size_t n = p.size();
-  std::string out;
-  size_t r = 0, dotdot = 0;
-  if (rooted) {
-    out.push_back('/');
-    r = dotdot = 1;
-  }
-  while (r < n) {
-    if (p[r] == '/') {
-      r++;
-    } else if (p[r] == '.' && (r + 1 == n || p[r + 1] == '/')) {
-      r++;
-    } else if (p[r] == '.' && r + 1 < n && p[r + 1] == '.' && (r + 2 == n || p[r + 2] == '/')) {
-      r += 2;
-      if (out.size() > dotdot) {
-        size_t w = out.size() - 1;
-        while (w > dotdot && out[w] != '/') w--;
-        out.resize(w);
-      } else if (!rooted) {
-        if (!out.empty()) out.push_back('/');
-        out += "..";
-        dotdot = out.size();
-      }
-    } else {
-      if ((rooted && out.size() != 1) || (!rooted && !out.empty())) out.push_back('/');
-      for (; r < n && p[r] != '/'; r++) out.push_back(p[r]);
-    }
-  }
-  return out.empty() ? "." : out;
-}
-
-std::string trim_slashes(const std::string& p, bool left, bool right) {
-  size_t a = 0, b = p.size();
-  while (left && a < b && p[a] == '/') a++;
-  while (right && b > a && p[b - 1] == '/') b--;
-  return p.substr(a, b - a);
-}
 
 bool is_dir(const std::string& p) { return !p.empty() && p.back() == '/'; }  // fileset.IsDir
 
@@ -193,12 +152,6 @@ bool path_is_child(const std::string& parent, const std::string& child) {  // pa
 thread_local std::string t_host_error;
 
 }  // namespace
-
-std::string clean_path(const std::string& p0) {  // paths.go:54-60
-  const std::string p = go_clean(p0);
-  if (p == ".") return "/";
-  return "/" + trim_slashes(p, true, true);
-}
 
 int source_arg(int kind, const char* arg, SrcArg* out, std::string* err) {
   out->kind = kind;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "index_list.h"
+#include "paths.h"
 
 namespace pfscdc {
 
@@ -27,7 +28,6 @@ struct SrcArg {
 // PFSCDC_EUNSUPPORTED (a glob pattern) / PFSCDC_EINVAL (an unknown kind) with *err set
 int source_arg(int kind, const char* arg, SrcArg* out, std::string* err);
 std::string source_not_found(const SrcArg& a);  // NewErrOnEmpty's text
-std::string clean_path(const std::string& p);   // paths.go:54-60
 
 // pfscdc_source_host over the internal types; *err names an error, *ndirs (nullable) = the
 // directory entries the inserter made that the filter selected

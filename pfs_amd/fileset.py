@@ -788,6 +788,50 @@ def last_diff_stats(chunker) -> dict:
     return out
 
 
+def _path_arg(p: str) -> bytes:
+    return p.encode("utf-8", "surrogateescape")
+
+
+def copy_map_host(lst: Optional[IndexList], src: str, dst: str, src_tag: str = "") -> IndexList:
+    """pfscdc_copy_map_host: CopyFile's selection and path transform of a level-0 list on the
+    host: the entries ``copyFile`` selects for ``src`` (and ``src_tag``, "" for every tag) with
+    their paths moved under ``dst``."""
+    lib = _lib.load()
+    out = C.c_void_p()
+    rc = lib.pfscdc_copy_map_host(lst._p if lst is not None else None, _path_arg(src),
+                                  _path_arg(src_tag), _path_arg(dst), C.byref(out))
+    if rc:
+        raise _lib.PfsCdcError(rc, "pfscdc_copy_map_host")
+    return IndexList(out)
+
+
+def copy_map(chunker, lst_or_dev, src: str, dst: str, src_tag: str = "") -> DevIndexList:
+    """pfscdc_dev_list_copy_map over a ``DevIndexList`` (pfscdc_copy_map_list over an
+    ``IndexList`` or None, uploaded first): on the device or on the host by the PFSCDC_COPY_MAP
+    knob, with the same result either way."""
+    out = C.c_void_p()
+    fn = chunker.lib.pfscdc_dev_list_copy_map if isinstance(lst_or_dev, DevIndexList) \
+        else chunker.lib.pfscdc_copy_map_list
+    rc = fn(chunker.ctx, lst_or_dev._p if lst_or_dev is not None else None, _path_arg(src),
+            _path_arg(src_tag), _path_arg(dst), C.byref(out))
+    if rc:
+        msg = chunker.lib.pfscdc_last_error(chunker.ctx)
+        raise _lib.PfsCdcError(rc, msg.decode("utf-8", "replace") if msg else "copy map")
+    return DevIndexList(out, chunker.device)
+
+
+def last_copy_map_stats(chunker) -> dict:
+    """Counts and stage times (ms) of the last copy_map on ``chunker``'s context."""
+    n, ms = (C.c_uint64 * 8)(), (C.c_float * 4)()
+    chunker.lib.pfscdc_last_copy_map_stats(chunker.ctx, n)
+    chunker.lib.pfscdc_last_copy_map_timings(chunker.ctx, ms)
+    out = dict(zip(["device", "entries_in", "entries_out", "datarefs_out", "blob_bytes_out",
+                    "h2d_bytes", "d2h_bytes"], [int(x) for x in n]))
+    out.update(zip(["count_ms", "fill_ms", "copy_ms", "guards_ms"],
+                   [round(float(x), 4) for x in ms]))
+    return out
+
+
 class _SourceTarStream(_DevTarStream):
     """GetFileTAR as the reference serves it: one tar entry per entry of a source's stream,
     directories included."""
@@ -1236,6 +1280,7 @@ class UnorderedWriter:
         self._chunker = storage._take_chunker()
         self.events: list = []  # per serialized fileset, its events in arrival order
         self.log: list = []  # every event as (fileset, ...) in arrival order
+        self.log_copied: list = []  # per event of log: a data chunk passed through by reference
         self._exc: Optional[BaseException] = None
         # the callback reaches the writer through a weak reference: a bound method here would
         # make a reference cycle, which the cyclic GC frees in arbitrary order, closing the
@@ -1278,6 +1323,7 @@ class UnorderedWriter:
                 e = ("index", ev.index, C.string_at(ev.bytes, ev.len))
             self.events[ev.fileset].append(e)
             self.log.append((ev.fileset,) + e)
+            self.log_copied.append(ev.kind == _lib.EV_CHUNK and bool(ev.chunk.copied))
             return 0
         except BaseException as e:
             self._exc = e
@@ -1299,6 +1345,42 @@ class UnorderedWriter:
 
     def delete(self, p: str, tag: str = "") -> None:
         self._check(self.lib.pfscdc_uw_delete(self._w, p.encode(), tag.encode()), "Delete")
+
+    def copy(self, files: Optional[IndexList], tag: str = "", append: bool = False) -> None:
+        """``UnorderedWriter.Copy``: the buffer is serialized, then every entry of ``files`` is
+        copied into one more fileset under ``tag`` ("": "default"), each after a Delete of its
+        (path, tag) unless ``append``.  Chunks the entries hold whole pass by reference."""
+        self._check(self.lib.pfscdc_uw_copy(self._w, files._p if files is not None else None,
+                                            tag.encode(), int(append)), "Copy")
+
+    def copy_file(self, src, src_path: str, dst: str, append: bool = False, tag: str = "",
+                  src_tag: str = "") -> None:
+        """``copyFile``: the file or subtree ``src_path`` of ``src`` under ``dst``.  ``src``: the
+        commit's filesets (what ``Storage.open`` takes), opened, selected, mapped and copied in
+        one call (pfscdc_uw_copy_file), or an opened ``FileSet``, whose resident list (or host
+        list, uploaded) goes through ``copy_map`` and ``copy``."""
+        if isinstance(src, FileSet):
+            c = Chunker(ChunkParams(), self._storage.device)
+            try:
+                dev = copy_map(c, src.resident if src.resident is not None else src._list,
+                               src_path, dst, src_tag)
+                try:
+                    mapped = dev.download(c)
+                finally:
+                    dev.free()
+            finally:
+                c.close()
+            try:
+                self.copy(mapped, tag, append)
+            finally:
+                mapped.free()
+            return
+        filesets = list(src)
+        arr, keep = Storage._infos(filesets)
+        self._check(self.lib.pfscdc_uw_copy_file(
+            self._w, arr, len(filesets), _path_arg(src_path), _path_arg(src_tag), _path_arg(dst),
+            tag.encode(), int(append)), "CopyFile")
+        del keep
 
     def timings(self) -> dict:
         """Stage times (ms) of this writer (pfscdc_uw_timings)."""

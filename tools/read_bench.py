@@ -74,8 +74,19 @@ diff's release and an upload of 16,384 entries, timed after every call so that n
 holds the other's leftovers), the counts and the bytes each way.  The arms' pairs
 and selections are compared array for array.  Writes profiles/r7/read_path/diff.json.
 
+--copy: CopyFile's selection and path transform (pfscdc_dev_list_copy_map) over resident lists of
+65,536 files of 4 KiB and of --files files of 256 B, at fan-out 64 and flat, the second half of
+each under /c instead of /b, so that src = /b selects half: the device arm (PFSCDC_COPY_MAP=1) and
+the host arm (0: download, pfscdc_copy_map_host, upload) alternating call by call.  Per arm:
+median, min and max of the call's stages and wall time (map_ms), and of the map together with
+what pfscdc_uw_copy needs next, the selection on the host (flow_ms: the device arm downloads its
+result; the host arm downloads the whole list and calls pfscdc_copy_map_host on it, with no
+upload).  The arms' arrays are compared.  One copy_file of a directory of 1,024 files of 256 KiB
+whose chunks pass by reference is recorded beside them.  Writes
+profiles/r7/read_path/copy.json.
+
 usage: python tools/read_bench.py [--tar | --index | --merge | --compact | --resident | --source
-                                   | --diff]
+                                   | --diff | --copy]
                                   [--chunks N]
                                   [--chunk-bytes B] [--files N] [--reps R] [--warmup W]
                                   [--out PATH]"""
@@ -786,6 +797,114 @@ def source_rows(args):
     return rows
 
 
+def copy_rows(args):
+    """--copy: pfscdc_dev_list_copy_map over a resident list whose first half lies under /b and
+    whose second half under /c, src = /b: the device arm (PFSCDC_COPY_MAP=1) and the host arm (0)
+    alternating call by call; per arm the map alone and the map with the selection brought to the
+    host, as pfscdc_uw_copy needs it.  The arms' arrays are compared."""
+    import time
+
+    from pfs_amd import fileset as PF
+    rows = []
+    keys = ["count_ms", "fill_ms", "copy_ms", "guards_ms", "map_ms", "flow_ms"]
+    shapes = [(65536, 4096), (args.files, 256)] if args.files != 65536 else [(65536, 4096)]
+    for nfiles, fbytes in shapes:
+        for flat in (False, True):
+            frames, _ = source_frames(nfiles, fbytes, flat, nfiles)
+            frames[nfiles // 2:, 11] = ord("c")  # /b/... becomes /c/...: still in path order
+            lst = PF.index_decode_host(frames.tobytes())
+            del frames
+            c = Chunker(ChunkParams(), 0)
+            dev = PF.DevIndexList.upload(c, lst)
+            runs = {1: [], 0: []}
+            last = {}
+            for i in range(args.warmup + args.reps):
+                for arm in (1, 0):
+                    _lib.set_knob("PFSCDC_COPY_MAP", arm)
+                    t0 = time.perf_counter()
+                    got = PF.copy_map(c, dev, "/b", "/copied/here")
+                    t1 = time.perf_counter()
+                    stats = PF.last_copy_map_stats(c)
+                    if stats["device"] != arm:
+                        raise SystemExit("read_bench: the wrong arm ran")
+                    if arm:  # the selection to the host
+                        host = got.download(c)
+                        flow = (time.perf_counter() - t0) * 1e3
+                    else:  # the whole list to the host, the selection made there
+                        t2 = time.perf_counter()
+                        whole = dev.download(c)
+                        host = PF.copy_map_host(whole, "/b", "/copied/here")
+                        flow = (time.perf_counter() - t2) * 1e3
+                        whole.free()
+                    if i == 0:
+                        check = got.download(c)
+                        last[arm] = (list_arrays(check), list_arrays(host))
+                        check.free()
+                        if last[arm][0] != last[arm][1] or (arm == 0 and last[0] != last[1]):
+                            raise SystemExit("read_bench: the device arm's list differs from the host arm's")
+                    host.free()
+                    got.free()
+                    if i >= args.warmup:
+                        stats["map_ms"] = (t1 - t0) * 1e3
+                        stats["flow_ms"] = flow
+                        runs[arm].append(stats)
+            row = {"files": nfiles, "file_bytes": fbytes, "layout": "flat" if flat else "fanout64",
+                   "src": "/b", "dst": "/copied/here", "reps": args.reps, "warmup": args.warmup,
+                   "device_equals_host": True,
+                   "stages": {"device": "count and prefix sums, fill, DataRef copy, guards",
+                              "host": "download, pfscdc_copy_map_host, upload, -"}}
+            for arm, name in ((1, "device"), (0, "host")):
+                r = runs[arm]
+                row[name] = {k: {"median": round(statistics.median(x[k] for x in r), 3),
+                                 "min": round(min(x[k] for x in r), 3),
+                                 "max": round(max(x[k] for x in r), 3)} for k in keys}
+                row[name].update({k: r[0][k] for k in ("entries_in", "entries_out", "datarefs_out",
+                                                       "blob_bytes_out", "h2d_bytes", "d2h_bytes")})
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            _lib.set_knob("PFSCDC_COPY_MAP", _lib.knob_info()["PFSCDC_COPY_MAP"][2])
+            dev.free()
+            lst.free()
+            c.close()
+    return rows
+
+
+def copy_file_row():
+    """One copy_file of a directory whose chunks pass by reference: 1,024 files of 256 KiB under
+    /d at the default chunking, copied to /moved."""
+    import time
+
+    from pfs_amd import chunk as pc
+    from pfs_amd import fileset as PF
+    from pfs_amd.cdc import synthetic_bytes
+    nfiles, fbytes = 1024, 256 << 10
+    st = PF.Storage(0, store=pc.ChunkStore())
+    body = synthetic_bytes([0, nfiles * fbytes], 77)
+    a = st.new_unordered_writer()
+    for k in range(nfiles):
+        a.put("/d/f%05d" % k, "", False, body[k * fbytes:(k + 1) * fbytes])
+    a.put("/other", "", False, b"other")
+    infos = a.close()
+    a.release()
+    w = st.new_unordered_writer()
+    t0 = time.perf_counter()
+    w.copy_file(infos, "/d", "/moved")
+    t1 = time.perf_counter()
+    got = w.close()
+    t2 = time.perf_counter()
+    data = [(e, c) for e, c in zip(w.log, w.log_copied) if e[1] == "chunk" and e[2] == -1]
+    w.release()
+    row = {"copy_file": "/d to /moved", "files": nfiles, "file_bytes": fbytes,
+           "copy_map_knob": _lib.get_knob("PFSCDC_COPY_MAP"),
+           "copy_file_ms": round((t1 - t0) * 1e3, 1), "close_ms": round((t2 - t1) * 1e3, 1),
+           "files_out": got[0].num_files, "size_bytes": got[0].size_bytes,
+           "data_chunks_by_reference": sum(1 for _, c in data if c),
+           "bytes_by_reference": int(sum(e[4] for e, c in data if c)),
+           "data_chunks_formed": sum(1 for _, c in data if not c)}
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--index", action="store_true")
@@ -794,6 +913,7 @@ def main():
     ap.add_argument("--resident", action="store_true")
     ap.add_argument("--source", action="store_true")
     ap.add_argument("--diff", action="store_true")
+    ap.add_argument("--copy", action="store_true")
     ap.add_argument("--files", type=int, default=1 << 20)
     ap.add_argument("--tar", action="store_true")
     ap.add_argument("--chunks", type=int, default=1024)
@@ -826,6 +946,18 @@ def main():
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/read_bench.py --source",
                        "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
+            f.write("\n")
+        return
+    if args.copy:
+        if args.out == os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json"):
+            args.out = os.path.join(ROOT, "profiles", "r7", "read_path", "copy.json")
+        rows = copy_rows(args)
+        record = copy_file_row()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/read_bench.py --copy",
+                       "device": torch.cuda.get_device_name(0),
+                       "copy": {"shapes": rows, "copy_file": record}}, f, indent=1)
             f.write("\n")
         return
     if args.diff:
