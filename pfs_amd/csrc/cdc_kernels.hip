@@ -2804,6 +2804,30 @@ __device__ inline int mrg_cmp(const MrgKey& a, const MrgKey& b) {
   return c ? c : mrg_cmp_str(a.t, a.tn, b.t, b.tn);
 }
 
+// What the fill kernels of the list passes share (the contract is in pfscdc_internal.h).
+// s[0, n) and a NUL at blob + at; the place after them
+PFS_DEV uint64_t put_str(char* blob, uint64_t at, const char* s, uint32_t n) {
+  for (uint32_t i = 0; i < n; i++) blob[at + i] = s[i];
+  blob[at + n] = 0;
+  return at + n + 1;
+}
+
+// o's path, tag and LastPath from src, where its offsets point, to blob + at, where they then point
+PFS_DEV void put_entry_strings(pfscdc_index_entry& o, const char* src, char* blob, uint64_t at) {
+  const uint64_t tag = put_str(blob, at, src + o.path_off, o.path_len);
+  const uint64_t last = put_str(blob, tag, src + o.tag_off, o.tag_len);
+  put_str(blob, last, src + o.last_path_off, o.last_path_len);
+  o.path_off = at;
+  o.tag_off = tag;
+  o.last_path_off = last;
+}
+
+// item i's ranges in the prefix sums are what it counts: else it writes nothing
+PFS_DEV bool ranges_are(const uint64_t* base, uint64_t i, MrgCount c) {
+  return base[3 * i + 3] - base[3 * i] == c.emit && base[3 * i + 4] - base[3 * i + 1] == c.recs &&
+         base[3 * i + 5] - base[3 * i + 2] == c.blob;
+}
+
 __global__ __launch_bounds__(kIdxBlock) void merge_rank_kernel(MrgIn in,
                                                                uint32_t* __restrict__ order,
                                                                uint32_t* __restrict__ bad) {
@@ -2957,28 +2981,16 @@ __global__ __launch_bounds__(kIdxBlock) void merge_fill_kernel(
   for (uint64_t p = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; p < in.n;
        p += (uint64_t)gridDim.x * kIdxBlock) {
     if (!cnt[p].emit) continue;
-    const uint64_t oi = base[3 * p], first = base[3 * p + 1], at0 = base[3 * p + 2];
-    const uint64_t cap = base[3 * p + 4] - first, room = base[3 * p + 5] - at0;
+    const uint64_t oi = base[3 * p], first = base[3 * p + 1], cap = base[3 * p + 4] - first;
     if (base[3 * p + 3] - oi != 1) continue;
     const MrgGroup r = mrg_walk(in, order, p, copy, first, cap);
-    if (!r.emit || r.recs != cap || r.blob != room) continue;  // (never: the count pass's walk)
+    // (never: the count pass's walk; recs compared in full, as cnt[] holds its low 32 bits)
+    if (!r.emit || r.recs != cap || !ranges_are(base, p, MrgCount{1, (uint32_t)cap, r.blob}))
+      continue;
     const uint64_t g0 = order[p];
     const pfscdc_index_entry e0 = in.entries[g0];
-    const char* src = in.blob + in.blob_base[mrg_stream(in, g0)];
     pfscdc_index_entry o = e0;
-    uint64_t at = at0;
-    o.path_off = at;
-    for (uint32_t i = 0; i < e0.path_len; i++) blob[at + i] = src[e0.path_off + i];
-    at += e0.path_len;
-    blob[at++] = 0;
-    o.tag_off = at;
-    for (uint32_t i = 0; i < e0.tag_len; i++) blob[at + i] = src[e0.tag_off + i];
-    at += e0.tag_len;
-    blob[at++] = 0;
-    o.last_path_off = at;
-    for (uint32_t i = 0; i < e0.last_path_len; i++) blob[at + i] = src[e0.last_path_off + i];
-    at += e0.last_path_len;
-    blob[at] = 0;
+    put_entry_strings(o, in.blob + in.blob_base[mrg_stream(in, g0)], blob, base[3 * p + 2]);
     o.first = (uint32_t)first;
     if (r.merged) {  // mergeIdx: the group's first entry with the merged File.DataRefs
       o.flags = (e0.flags & ~(PFSCDC_IDX_HAS_CHUNK_REF | PFSCDC_IDX_HAS_RANGE)) | PFSCDC_IDX_HAS_FILE;
@@ -3033,11 +3045,11 @@ hipError_t launch_merge_fill(const MrgIn& in, const uint32_t* order, const MrgCo
   return hipGetLastError();
 }
 
-hipError_t launch_merge_copy(const MrgIn& in, const MrgCopy* copy, pfscdc_full_dataref* drs,
-                             int num_cus, hipStream_t st) {
-  if (in.n == 0) return hipSuccess;
-  merge_copy_kernel<<<merge_grid(in.n * 8, num_cus), kIdxBlock, 0, st>>>(
-      (const uint4*)in.drs, copy, in.n, (uint4*)drs);
+hipError_t launch_list_copy(const pfscdc_full_dataref* src, const MrgCopy* copy, uint64_t n,
+                            pfscdc_full_dataref* dst, int num_cus, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  merge_copy_kernel<<<merge_grid(n * 8, num_cus), kIdxBlock, 0, st>>>((const uint4*)src, copy, n,
+                                                                     (uint4*)dst);
   return hipGetLastError();
 }
 
@@ -3426,6 +3438,46 @@ PFS_DEV bool src_entry_ok(const RtarList& in, const pfscdc_index_entry& e) {
          e.count <= in.nr - e.first;
 }
 
+// IsClean(p, false) for s[0, n): rooted, no empty component, none of "." or ".."; with
+// allow_trailing_slash IsClean(p, IsDir(p)): the last component may be empty
+PFS_DEV bool path_is_clean(const uint8_t* s, uint32_t n, bool allow_trailing_slash) {
+  bool clean = n > 0 && s[0] == '/';
+  for (uint32_t k = 1, start = 1; clean && k <= n; k++) {
+    if (k < n && s[k] != '/') continue;
+    const uint32_t cl = k - start;
+    if (cl == 0) clean = allow_trailing_slash && k == n;
+    else if (cl == 1) clean = s[start] != '.';
+    else if (cl == 2) clean = s[start] != '.' || s[start + 1] != '.';
+    start = k + 1;
+  }
+  return clean;
+}
+
+// Entry i > 0 (e, inside the arrays) against the entry before it.  false and kSrcMalformed in
+// *bad: that one lies outside the arrays.  Else *bad |= kSrcUnordered if it is above e by path,
+// then tag; *lcp the two paths' common prefix, *same whether they are one path.
+PFS_DEV bool src_follows(const RtarList& in, uint64_t i, const pfscdc_index_entry& e, uint32_t* bad,
+                         uint32_t* lcp, bool* same) {
+  const pfscdc_index_entry q = in.entries[i - 1];
+  if (!src_entry_ok(in, q)) {
+    *bad |= kSrcMalformed;
+    return false;
+  }
+  const uint8_t* s = (const uint8_t*)in.blob + e.path_off;
+  const uint8_t* t = (const uint8_t*)in.blob + q.path_off;
+  const uint32_t n = e.path_len, m = n < q.path_len ? n : q.path_len;
+  uint32_t l = 0;
+  while (l < m && s[l] == t[l]) l++;
+  int cmp = l < m ? (t[l] < s[l] ? -1 : 1) : q.path_len < n ? -1 : q.path_len > n ? 1 : 0;
+  *lcp = l;
+  *same = cmp == 0;
+  if (cmp == 0)
+    cmp = mrg_cmp_str((const uint8_t*)in.blob + q.tag_off, q.tag_len,
+                      (const uint8_t*)in.blob + e.tag_off, e.tag_len);
+  if (cmp > 0) *bad |= kSrcUnordered;
+  return true;
+}
+
 // What input entry i emits, *lcp its common prefix with the entry before, *bad |= SrcBad.
 PFS_DEV MrgCount src_item(const RtarList& in, const SrcPred& pr, uint64_t i, uint32_t* bad,
                           uint32_t* lcp) {
@@ -3439,37 +3491,13 @@ PFS_DEV MrgCount src_item(const RtarList& in, const SrcPred& pr, uint64_t i, uin
   if (e.flags & (PFSCDC_IDX_HAS_RANGE | PFSCDC_IDX_HAS_CHUNK_REF)) *bad |= kSrcNotLevel0;
   const uint8_t* s = (const uint8_t*)in.blob + e.path_off;
   const uint32_t n = e.path_len;
-  // IsClean(p, IsDir(p)): rooted, no empty component but a last one, none of "." or ".."
-  bool clean = n > 0 && s[0] == '/';
-  for (uint32_t k = 1, start = 1; clean && k <= n; k++) {
-    if (k < n && s[k] != '/') continue;
-    const uint32_t cl = k - start;
-    if (cl == 0) clean = k == n;
-    else if (cl == 1) clean = s[start] != '.';
-    else if (cl == 2) clean = s[start] != '.' || s[start + 1] != '.';
-    start = k + 1;
-  }
-  if (!clean) *bad |= kSrcUnclean;
-  uint32_t l = 0;
+  if (!path_is_clean(s, n, true)) *bad |= kSrcUnclean;
   if (i > 0) {
-    const pfscdc_index_entry q = in.entries[i - 1];
-    if (!src_entry_ok(in, q)) {
-      *bad |= kSrcMalformed;
-      return c;
-    }
-    const uint8_t* t = (const uint8_t*)in.blob + q.path_off;
-    const uint32_t m = n < q.path_len ? n : q.path_len;
-    while (l < m && s[l] == t[l]) l++;
-    int cmp = l < m ? (t[l] < s[l] ? -1 : 1) : q.path_len < n ? -1 : q.path_len > n ? 1 : 0;
-    if (cmp == 0) {
-      if (n && s[n - 1] == '/') *bad |= kSrcDirTwice;
-      cmp = mrg_cmp_str((const uint8_t*)in.blob + q.tag_off, q.tag_len,
-                        (const uint8_t*)in.blob + e.tag_off, e.tag_len);
-    }
-    if (cmp > 0) *bad |= kSrcUnordered;
+    bool same;
+    if (!src_follows(in, i, e, bad, lcp, &same)) return c;
+    if (same && n && s[n - 1] == '/') *bad |= kSrcDirTwice;
   }
-  *lcp = l;
-  for (uint32_t k = l; k + 1 < n; k++)
+  for (uint32_t k = *lcp; k + 1 < n; k++)
     if (s[k] == '/' && src_selected(pr, s, k + 1)) {
       c.emit++;
       c.blob += (uint64_t)k + 4;  // the path and three NULs (path, empty tag, empty LastPath)
@@ -3505,9 +3533,7 @@ __global__ __launch_bounds__(kIdxBlock) void src_fill_kernel(
     const uint64_t first = base[3 * i + 1];
     uint32_t b = 0, lcp;
     const MrgCount c = src_item(in, pr, i, &b, &lcp);
-    if (b || c.emit != base[3 * i + 3] - oi || c.recs != base[3 * i + 4] - first ||
-        c.blob != base[3 * i + 5] - at)
-      continue;  // (never: the count pass's walk)
+    if (b || !ranges_are(base, i, c)) continue;  // (never: the count pass's walk)
     const pfscdc_index_entry e = in.entries[i];
     const uint8_t* s = (const uint8_t*)in.blob + e.path_off;
     const uint32_t n = e.path_len;
@@ -3518,17 +3544,17 @@ __global__ __launch_bounds__(kIdxBlock) void src_fill_kernel(
       if (src_selected(pr, s, k + 1)) {  // dirFile.Index(): Index{Path: dir, File: {}}
         pfscdc_index_entry o;
         o.path_off = at;
-        o.tag_off = at + k + 2;
-        o.last_path_off = at + k + 3;
+        at = put_str(blob, at, (const char*)s, k + 1);
+        o.tag_off = at;  // an empty tag, an empty LastPath
+        at = put_str(blob, at, nullptr, 0);
+        o.last_path_off = at;
+        at = put_str(blob, at, nullptr, 0);
         o.path_len = k + 1;
         o.tag_len = o.last_path_len = 0;
         o.flags = PFSCDC_IDX_HAS_FILE;
         o.first = (uint32_t)first;
         o.count = 0;
         o.size_bytes = o.range_offset = 0;
-        for (uint32_t x = 0; x <= k; x++) blob[at + x] = (char)s[x];
-        blob[at + k + 1] = blob[at + k + 2] = blob[at + k + 3] = 0;
-        at += (uint64_t)k + 4;
         entries[oi] = o;
         meta[oi] = SrcMeta{kSrcDir, depth, 0};
         infos[oi].size = 0;
@@ -3542,20 +3568,8 @@ __global__ __launch_bounds__(kIdxBlock) void src_fill_kernel(
       depth++;
     }
     if (!src_selected(pr, s, n)) continue;
-    const char* src = in.blob;
     pfscdc_index_entry o = e;
-    o.path_off = at;
-    for (uint32_t x = 0; x < n; x++) blob[at + x] = (char)s[x];
-    at += n;
-    blob[at++] = 0;
-    o.tag_off = at;
-    for (uint32_t x = 0; x < e.tag_len; x++) blob[at + x] = src[e.tag_off + x];
-    at += e.tag_len;
-    blob[at++] = 0;
-    o.last_path_off = at;
-    for (uint32_t x = 0; x < e.last_path_len; x++) blob[at + x] = src[e.last_path_off + x];
-    at += e.last_path_len;
-    blob[at] = 0;
+    put_entry_strings(o, in.blob, blob, at);
     o.first = (uint32_t)first;
     entries[oi] = o;
     if (e.count) copy[i] = MrgCopy{(uint32_t)first, e.count, e.first, 0};
@@ -3692,9 +3706,7 @@ hipError_t launch_src_fill(const RtarList& in, const SrcPred& pr, const MrgCount
   if (in.n == 0) return hipSuccess;
   src_fill_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(
       in, pr, cnt, base, entries, blob, copy, meta, infos, sizes, maxdepth);
-  merge_copy_kernel<<<merge_grid(in.n * 8, num_cus), kIdxBlock, 0, st>>>(
-      (const uint4*)in.drs, copy, in.n, (uint4*)drs);
-  return hipGetLastError();
+  return launch_list_copy(in.drs, copy, in.n, drs, num_cus, st);
 }
 
 hipError_t launch_src_tree(const RtarList& out, SrcMeta* meta, const uint64_t* sbase,
@@ -3854,25 +3866,11 @@ __global__ __launch_bounds__(kIdxBlock) void diff_select_kernel(
        i += (uint64_t)gridDim.x * kIdxBlock) {
     if (!sel[i].emit) continue;
     const uint64_t oi = base[3 * i], first = base[3 * i + 1];
-    uint64_t at = base[3 * i + 2];
     const pfscdc_index_entry e = in.l.entries[i];
-    if (base[3 * i + 3] - oi != 1 || base[3 * i + 4] - first != e.count ||
-        base[3 * i + 5] - at != (uint64_t)e.path_len + e.tag_len + e.last_path_len + 3)
-      continue;  // (never: the rank pass's counts)
-    const char* src = in.l.blob;
+    const uint64_t room = (uint64_t)e.path_len + e.tag_len + e.last_path_len + 3;
+    if (!ranges_are(base, i, MrgCount{1, e.count, room})) continue;  // (never: the rank pass's counts)
     pfscdc_index_entry o = e;
-    o.path_off = at;
-    for (uint32_t x = 0; x < e.path_len; x++) blob[at + x] = src[e.path_off + x];
-    at += e.path_len;
-    blob[at++] = 0;
-    o.tag_off = at;
-    for (uint32_t x = 0; x < e.tag_len; x++) blob[at + x] = src[e.tag_off + x];
-    at += e.tag_len;
-    blob[at++] = 0;
-    o.last_path_off = at;
-    for (uint32_t x = 0; x < e.last_path_len; x++) blob[at + x] = src[e.last_path_off + x];
-    at += e.last_path_len;
-    blob[at] = 0;
+    put_entry_strings(o, in.l.blob, blob, base[3 * i + 2]);
     o.first = (uint32_t)first;
     entries[oi] = o;
     if (e.count) copy[i] = MrgCopy{(uint32_t)first, e.count, e.first, 0};
@@ -3904,9 +3902,7 @@ hipError_t launch_diff_select(const DiffSide& in, const MrgCount* sel, const uin
   if (in.l.n == 0) return hipSuccess;
   diff_select_kernel<<<merge_grid(in.l.n, num_cus), kIdxBlock, 0, st>>>(in, sel, base, entries,
                                                                        blob, copy, infos);
-  merge_copy_kernel<<<merge_grid(in.l.n * 8, num_cus), kIdxBlock, 0, st>>>(
-      (const uint4*)in.l.drs, copy, in.l.n, (uint4*)drs);
-  return hipGetLastError();
+  return launch_list_copy(in.l.drs, copy, in.l.n, drs, num_cus, st);
 }
 
 // ---- 13. CopyFile: a subtree selected and moved under a new root -------------------------------
@@ -3953,16 +3949,9 @@ PFS_DEV CmapItem cmap_item(const RtarList& in, const CmapPred& pr, uint64_t i, u
   const uint8_t* s = (const uint8_t*)in.blob + e.path_off;
   const uint8_t* t = (const uint8_t*)in.blob + e.tag_off;
   const uint32_t n = e.path_len;
-  if (i > 0) {
-    const pfscdc_index_entry q = in.entries[i - 1];
-    if (!src_entry_ok(in, q)) {
-      *bad |= kSrcMalformed;
-      return it;
-    }
-    int cmp = mrg_cmp_str((const uint8_t*)in.blob + q.path_off, q.path_len, s, n);
-    if (cmp == 0) cmp = mrg_cmp_str((const uint8_t*)in.blob + q.tag_off, q.tag_len, t, e.tag_len);
-    if (cmp > 0) *bad |= kSrcUnordered;
-  }
+  uint32_t lcp;
+  bool same;
+  if (i > 0 && !src_follows(in, i, e, bad, &lcp, &same)) return it;
   if (pr.tag_len) {  // index.WithTag
     bool eq = e.tag_len == pr.tag_len;
     for (uint32_t k = 0; eq && k < pr.tag_len; k++) eq = t[k] == (uint8_t)pr.tag[k];
@@ -3973,16 +3962,7 @@ PFS_DEV CmapItem cmap_item(const RtarList& in, const CmapPred& pr, uint64_t i, u
   for (uint32_t k = 0; k < pr.src_len; k++)
     if (s[k] != (uint8_t)pr.src[k]) return it;
   if (n > pr.src_len && s[pr.src_len] != '/') return it;
-  // IsClean(p, false)
-  bool clean = n > 0 && s[0] == '/';
-  for (uint32_t k = 1, start = 1; clean && k <= n; k++) {
-    if (k < n && s[k] != '/') continue;
-    const uint32_t cl = k - start;
-    if (cl == 0) clean = false;
-    else if (cl == 1) clean = s[start] != '.';
-    else if (cl == 2) clean = s[start] != '.' || s[start + 1] != '.';
-    start = k + 1;
-  }
+  const bool clean = path_is_clean(s, n, false);
   it.keep = n - pr.src_len;
   it.root = (it.keep && pr.dst_len == 1) ? 0 : pr.dst_len;  // dstPath "/" + "/tail" is "/tail"
   const uint64_t len = (uint64_t)it.root + it.keep;
@@ -4012,27 +3992,18 @@ __global__ __launch_bounds__(kIdxBlock) void cmap_fill_kernel(
     uint64_t at = base[3 * i + 2];
     uint32_t b = 0;
     const CmapItem it = cmap_item(in, pr, i, &b);
-    if (b || base[3 * i + 3] - oi != 1 || base[3 * i + 4] - first != it.c.recs ||
-        base[3 * i + 5] - at != it.c.blob)
-      continue;  // (never: the count pass's walk)
+    if (b || !ranges_are(base, i, it.c)) continue;  // (never: the count pass's walk)
     const pfscdc_index_entry e = in.entries[i];
-    const char* src = in.blob;
     pfscdc_index_entry o = e;
     o.path_off = at;
     o.path_len = it.root + it.keep;
-    for (uint32_t x = 0; x < it.root; x++) blob[at + x] = pr.dst[x];
-    at += it.root;
-    const uint64_t tail = e.path_off + (e.path_len - it.keep);
-    for (uint32_t x = 0; x < it.keep; x++) blob[at + x] = src[tail + x];
-    at += it.keep;
-    blob[at++] = 0;
+    at = put_str(blob, at, pr.dst, it.root) - 1;  // the new root; the tail goes over its NUL
+    at = put_str(blob, at, in.blob + e.path_off + (e.path_len - it.keep), it.keep);
     o.tag_off = at;
-    for (uint32_t x = 0; x < e.tag_len; x++) blob[at + x] = src[e.tag_off + x];
-    at += e.tag_len;
-    blob[at++] = 0;
+    at = put_str(blob, at, in.blob + e.tag_off, e.tag_len);
     o.last_path_off = at;
     o.last_path_len = 0;
-    blob[at] = 0;
+    put_str(blob, at, nullptr, 0);
     o.first = (uint32_t)first;
     entries[oi] = o;
     if (e.count) copy[i] = MrgCopy{(uint32_t)first, e.count, e.first, 0};
@@ -4052,14 +4023,6 @@ hipError_t launch_cmap_fill(const RtarList& in, const CmapPred& pr, const MrgCou
   if (in.n == 0) return hipSuccess;
   cmap_fill_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(in, pr, cnt, base, entries,
                                                                    blob, copy);
-  return hipGetLastError();
-}
-
-hipError_t launch_cmap_copy(const RtarList& in, const MrgCopy* copy, pfscdc_full_dataref* drs,
-                            int num_cus, hipStream_t st) {
-  if (in.n == 0) return hipSuccess;
-  merge_copy_kernel<<<merge_grid(in.n * 8, num_cus), kIdxBlock, 0, st>>>(
-      (const uint4*)in.drs, copy, in.n, (uint4*)drs);
   return hipGetLastError();
 }
 

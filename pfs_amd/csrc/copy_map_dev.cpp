@@ -1,47 +1,20 @@
 // copy_map_dev.cpp — CopyFile's selection and path transform over a device-resident list
 // (pfscdc_dev_list_copy_map): the driver of the cmap_* kernels (cdc_kernels.hip §13) and the
 // hand-over to the host arm (copy_map.cpp).
-#include <chrono>
-#include <cstring>
 #include <memory>
 #include <string>
 
 #include "copy_map.h"
-#include "dev_list.h"
-#include "index_list.h"
-#include "pfscdc_internal.h"
+#include "dev_pass.h"
 
 namespace {
 
 using namespace pfscdc;
 using List = pfscdc_index_list;
 
-#define CMAP_HIP(ctx, expr)                                                            \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return pfscdc::ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PFSCDC_ENOMEM : PFSCDC_EHIP, \
-                              std::string(#expr) + ": " + hipGetErrorString(e_));      \
-  } while (0)
-
-struct Clock {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  float lap() {  // ms since the last lap
-    const auto t1 = std::chrono::steady_clock::now();
-    const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-    t0 = t1;
-    return ms;
-  }
-};
-
-uint64_t list_bytes(const List& l) {
-  return sizeof(pfscdc_index_entry) * l.entries.size() + sizeof(pfscdc_full_dataref) * l.drs.size() +
-         l.blob.size();
-}
-
 // The host arm: the list comes to the host, pfscdc_copy_map_host's body runs, its result goes back.
 int host_arm(pfscdc_ctx* ctx, const pfscdc_dev_list& in, const CopyArg& a, pfscdc_dev_list** out) {
-  CopyMapStats& st = ctx_copy_map_stats(ctx);
+  PassStats& st = ctx_copy_map_stats(ctx);
   Clock clk;
   List l, res;
   if (int rc = dev_list_download(ctx, in, &l)) return rc;
@@ -61,41 +34,40 @@ int host_arm(pfscdc_ctx* ctx, const pfscdc_dev_list& in, const CopyArg& a, pfscd
 
 int copy_map(pfscdc_ctx* ctx, const pfscdc_dev_list& in, const CopyArg& a, pfscdc_dev_list** out) {
   *out = nullptr;
-  CopyMapStats& st = ctx_copy_map_stats(ctx);
-  st = CopyMapStats();
+  PassStats& st = ctx_copy_map_stats(ctx);
+  st = PassStats();
   st.n[1] = in.n;
   if (in.device != ctx_device(ctx))
     return ctx_fail(ctx, PFSCDC_EINVAL, "a resident list of another device");
-  CMAP_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
   if (knob(Knob::CopyMap) == 0) return host_arm(ctx, in, a, out);
   hipStream_t s = ctx_stream(ctx);
   const int cus = ctx_num_cus(ctx);
-  const RtarList l{(const pfscdc_index_entry*)in.entries, (const char*)in.blob,
-                   (const pfscdc_full_dataref*)in.drs, in.n, in.nr, in.nb};
+  const RtarList l = view(in);
   Clock clk;
   // ---- select: count, prefix sums
   GuardMem d_arg, d_cnt, d_base, d_bad;
   Guards g;
   const std::string args = a.src + a.dst + a.tag;
-  CMAP_HIP(ctx, d_arg.alloc(args.size(), s));
-  CMAP_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * l.n, s));
-  CMAP_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (l.n + 1), s));
-  CMAP_HIP(ctx, d_bad.alloc(sizeof(uint32_t), s));
+  PFS_HIP(ctx, d_arg.alloc(args.size(), s));
+  PFS_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * l.n, s));
+  PFS_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (l.n + 1), s));
+  PFS_HIP(ctx, d_bad.alloc(sizeof(uint32_t), s));
   for (const GuardMem* x : {&d_cnt, &d_base, &d_bad}) g.add(*x);
-  CMAP_HIP(ctx, hipMemcpyAsync(d_arg.p, args.data(), args.size(), hipMemcpyHostToDevice, s));
+  PFS_HIP(ctx, hipMemcpyAsync(d_arg.p, args.data(), args.size(), hipMemcpyHostToDevice, s));
   st.n[5] += args.size();
-  CMAP_HIP(ctx, hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
+  PFS_HIP(ctx, hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
   const CmapPred pr{d_arg.as<char>(), d_arg.as<char>() + a.src.size(),
                     d_arg.as<char>() + a.src.size() + a.dst.size(), (uint32_t)a.src.size(),
                     (uint32_t)a.dst.size(), (uint32_t)a.tag.size(), 0};
-  CMAP_HIP(ctx, launch_cmap_count(l, pr, d_cnt.as<MrgCount>(), d_bad.as<uint32_t>(), cus, s));
-  CMAP_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), l.n, d_base.as<uint64_t>(), s));
+  PFS_HIP(ctx, launch_cmap_count(l, pr, d_cnt.as<MrgCount>(), d_bad.as<uint32_t>(), cus, s));
+  PFS_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), l.n, d_base.as<uint64_t>(), s));
   uint64_t totals[3] = {0, 0, 0};
   uint32_t bad = 0;
-  CMAP_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 3 * l.n, sizeof totals,
-                               hipMemcpyDeviceToHost, s));
-  CMAP_HIP(ctx, hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
-  CMAP_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 3 * l.n, sizeof totals,
+                              hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   st.n[6] += sizeof totals + sizeof bad;
   if (bad & kSrcMalformed)
     return ctx_fail(ctx, PFSCDC_EINVAL, "an entry's strings or DataRefs lie outside the list's arrays");
@@ -105,38 +77,29 @@ int copy_map(pfscdc_ctx* ctx, const pfscdc_dev_list& in, const CopyArg& a, pfscd
   const uint64_t m = totals[0], nr = totals[1], nb = totals[2];
   if (m > l.n || nr > l.nr) return ctx_fail(ctx, PFSCDC_EHIP, "copy map: the counts exceed the input");
   // ---- fill: entries and strings, then the DataRefs
-  GuardMem o_entries, o_blob, o_drs, d_copy;
-  CMAP_HIP(ctx, o_entries.alloc(sizeof(pfscdc_index_entry) * m, s));
-  CMAP_HIP(ctx, o_blob.alloc(nb, s));
-  CMAP_HIP(ctx, o_drs.alloc(sizeof(pfscdc_full_dataref) * nr, s));
-  CMAP_HIP(ctx, d_copy.alloc(sizeof(MrgCopy) * l.n, s));
-  for (const GuardMem* x : {&o_entries, &o_blob, &o_drs, &d_copy}) g.add(*x);
-  if (l.n) CMAP_HIP(ctx, hipMemsetAsync(d_copy.p, 0, sizeof(MrgCopy) * l.n, s));
-  CMAP_HIP(ctx, launch_cmap_fill(l, pr, d_cnt.as<MrgCount>(), d_base.as<uint64_t>(),
-                                 o_entries.as<pfscdc_index_entry>(), o_blob.as<char>(),
-                                 d_copy.as<MrgCopy>(), cus, s));
-  CMAP_HIP(ctx, hipStreamSynchronize(s));
+  OutList o;
+  GuardMem d_copy;
+  PFS_HIP(ctx, o.alloc(totals, s, &g));
+  PFS_HIP(ctx, copy_plan_alloc(&d_copy, l.n, s, &g));
+  PFS_HIP(ctx, launch_cmap_fill(l, pr, d_cnt.as<MrgCount>(), d_base.as<uint64_t>(),
+                                o.entries.as<pfscdc_index_entry>(), o.blob.as<char>(),
+                                d_copy.as<MrgCopy>(), cus, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   st.ms[1] = clk.lap();
-  CMAP_HIP(ctx, launch_cmap_copy(l, d_copy.as<MrgCopy>(), o_drs.as<pfscdc_full_dataref>(), cus, s));
-  CMAP_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, launch_list_copy(l.drs, d_copy.as<MrgCopy>(), l.n, o.drs.as<pfscdc_full_dataref>(),
+                                cus, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   st.ms[2] = clk.lap();
-  CMAP_HIP(ctx, g.fetch(s));
-  CMAP_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, g.fetch(s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   st.n[6] += g.host.size();
   if (!g.ok()) return ctx_fail(ctx, PFSCDC_EHIP, "copy map: a kernel wrote past its array");
   st.ms[3] = clk.lap();
-  pfscdc_dev_list* d = dev_list_new(ctx);
-  d->n = m;
-  d->nr = nr;
-  d->nb = nb;
-  d->entries = o_entries.release();
-  d->blob = o_blob.release();
-  d->drs = o_drs.release();
   st.n[0] = 1;
   st.n[2] = m;
   st.n[3] = nr;
   st.n[4] = nb;
-  *out = d;
+  *out = o.release(ctx);
   return PFSCDC_OK;
 }
 
@@ -166,15 +129,11 @@ int pfscdc_copy_map_list(pfscdc_ctx* ctx, const pfscdc_index_list* in, const cha
 }
 
 int pfscdc_last_copy_map_stats(pfscdc_ctx* ctx, uint64_t out[8]) {
-  if (!ctx || !out) return PFSCDC_EINVAL;
-  std::memcpy(out, pfscdc::ctx_copy_map_stats(ctx).n, sizeof(uint64_t) * 8);
-  return PFSCDC_OK;
+  return pfscdc::last_pass_stats(ctx, pfscdc::ctx_copy_map_stats, out, nullptr);
 }
 
 int pfscdc_last_copy_map_timings(pfscdc_ctx* ctx, float out[4]) {
-  if (!ctx || !out) return PFSCDC_EINVAL;
-  std::memcpy(out, pfscdc::ctx_copy_map_stats(ctx).ms, sizeof(float) * 4);
-  return PFSCDC_OK;
+  return pfscdc::last_pass_stats(ctx, pfscdc::ctx_copy_map_stats, nullptr, out);
 }
 
 }  // extern "C"

@@ -40,52 +40,6 @@ struct ResidentStats {
 };
 ResidentStats& ctx_resident_stats(pfscdc_ctx* ctx);
 
-constexpr uint64_t kGuard = 64;
-
-// A device array a planning kernel fills, 64 bytes longer than the kernel may write; the guard
-// is preset to 0xA5 and read back by Guards::fetch.
-struct GuardMem {
-  void* p = nullptr;
-  uint64_t bytes = 0;
-  ~GuardMem() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(uint64_t n, hipStream_t s) {
-    bytes = n;
-    hipError_t e = hipMalloc(&p, n + kGuard);
-    if (e != hipSuccess) return e;
-    return hipMemsetAsync((char*)p + n, 0xA5, kGuard, s);
-  }
-  void* release() {
-    void* r = p;
-    p = nullptr;
-    return r;
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
-
-struct Guards {
-  std::vector<const GuardMem*> mems;
-  std::vector<uint8_t> host;
-  void add(const GuardMem& m) { mems.push_back(&m); }
-  // enqueue the guards' copies; after the stream is synchronised ok() tells whether all stand
-  hipError_t fetch(hipStream_t s) {
-    host.assign(mems.size() * kGuard, 0);
-    for (size_t i = 0; i < mems.size(); i++) {
-      hipError_t e = hipMemcpyAsync(host.data() + i * kGuard, (const char*)mems[i]->p + mems[i]->bytes,
-                                    kGuard, hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
-  bool ok() const {
-    for (uint8_t b : host)
-      if (b != 0xA5) return false;
-    return true;
-  }
-};
-
 // A handle on ctx's device with no arrays yet (an empty list; arrays of a count of 0 may stay
 // NULL).
 pfscdc_dev_list* dev_list_new(pfscdc_ctx* ctx);

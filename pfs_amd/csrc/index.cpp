@@ -12,15 +12,12 @@
 //   stream/priority_queue.go:103-127         groups of equal streams, sorted by priority
 //   pbutil/pbutil.go:39,65                   int64 LE length + proto
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "dev_list.h"
-#include "index_list.h"
-#include "pfscdc_internal.h"
+#include "dev_pass.h"
 
 namespace {
 
@@ -64,29 +61,6 @@ bool select(const List& l, const IdxFilter& f, std::vector<uint32_t>* sel,
   return true;
 }
 
-struct DevMem {  // hipMalloc'ed for the call
-  void* p = nullptr;
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
-
-using Clock = std::chrono::steady_clock;
-float ms_since(Clock::time_point t0) {
-  return std::chrono::duration<float, std::milli>(Clock::now() - t0).count();
-}
-
-#define IDX_HIP(ctx, expr)                                                             \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return pfscdc::ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PFSCDC_ENOMEM : PFSCDC_EHIP, \
-                              std::string(#expr) + ": " + hipGetErrorString(e_));      \
-  } while (0)
-
 int corrupt(pfscdc_ctx* ctx, uint32_t level, uint64_t offset) {
   return pfscdc::ctx_fail(ctx, PFSCDC_ECORRUPT,
                           "index level " + std::to_string(level) + ": the frame at stream offset " +
@@ -104,7 +78,7 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
   hipStream_t s = ctx_stream(ctx);
   const int cus = ctx_num_cus(ctx);
   const uint64_t start0 = cb[0] + (uint64_t)off[0];
-  auto t0 = Clock::now();
+  Clock clk;
   // ---- the frame walk: one speculative walker per chunk, settled along the chain
   std::vector<IdxWalk> walks(nc);
   for (uint32_t i = 0; i < nc; i++) {
@@ -114,15 +88,15 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
                        len / 8 + 1};
   }
   DevMem d_walks, d_outs, d_starts;
-  IDX_HIP(ctx, d_walks.alloc(sizeof(IdxWalk) * nc));
-  IDX_HIP(ctx, d_outs.alloc(sizeof(IdxWalkOut) * nc));
-  IDX_HIP(ctx, d_starts.alloc(sizeof(uint64_t) * (n / 8 + nc + 1)));
-  IDX_HIP(ctx, hipMemcpyAsync(d_walks.p, walks.data(), sizeof(IdxWalk) * nc, hipMemcpyHostToDevice, s));
-  IDX_HIP(ctx, launch_index_walk(d_buf, n, d_walks.as<IdxWalk>(), nc, d_starts.as<uint64_t>(),
+  PFS_HIP(ctx, d_walks.alloc(sizeof(IdxWalk) * nc));
+  PFS_HIP(ctx, d_outs.alloc(sizeof(IdxWalkOut) * nc));
+  PFS_HIP(ctx, d_starts.alloc(sizeof(uint64_t) * (n / 8 + nc + 1)));
+  PFS_HIP(ctx, hipMemcpyAsync(d_walks.p, walks.data(), sizeof(IdxWalk) * nc, hipMemcpyHostToDevice, s));
+  PFS_HIP(ctx, launch_index_walk(d_buf, n, d_walks.as<IdxWalk>(), nc, d_starts.as<uint64_t>(),
                                  d_outs.as<IdxWalkOut>(), cus, s));
   std::vector<IdxWalkOut> outs(nc);
-  IDX_HIP(ctx, hipMemcpyAsync(outs.data(), d_outs.p, sizeof(IdxWalkOut) * nc, hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, hipMemcpyAsync(outs.data(), d_outs.p, sizeof(IdxWalkOut) * nc, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   // The truth is the chain from chunk 0's claim: chunk i's walk stands only if the chunk
   // before is settled and its exit is chunk i's claim.  A chunk wholly inside one entry (its
   // one annotation gets Offset 0, index/writer.go:102-121) holds no frame start at all; any
@@ -140,13 +114,13 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
         outs[i] = IdxWalkOut{from, 0, kIdxNone, 0};
       } else {
         walks[i].start = from;
-        IDX_HIP(ctx, hipMemcpyAsync(d_walks.as<IdxWalk>() + i, &walks[i], sizeof(IdxWalk),
+        PFS_HIP(ctx, hipMemcpyAsync(d_walks.as<IdxWalk>() + i, &walks[i], sizeof(IdxWalk),
                                     hipMemcpyHostToDevice, s));
-        IDX_HIP(ctx, launch_index_walk(d_buf, n, d_walks.as<IdxWalk>() + i, 1,
+        PFS_HIP(ctx, launch_index_walk(d_buf, n, d_walks.as<IdxWalk>() + i, 1,
                                        d_starts.as<uint64_t>(), d_outs.as<IdxWalkOut>() + i, cus, s));
-        IDX_HIP(ctx, hipMemcpyAsync(&outs[i], d_outs.as<IdxWalkOut>() + i, sizeof(IdxWalkOut),
+        PFS_HIP(ctx, hipMemcpyAsync(&outs[i], d_outs.as<IdxWalkOut>() + i, sizeof(IdxWalkOut),
                                     hipMemcpyDeviceToHost, s));
-        IDX_HIP(ctx, hipStreamSynchronize(s));
+        PFS_HIP(ctx, hipStreamSynchronize(s));
       }
     }
     nf += outs[i].count;
@@ -162,53 +136,52 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
       break;
     }
   }
-  st.ms[2] += ms_since(t0);
+  st.ms[2] += clk.lap();
   st.n[3] += nf;
   if (nf == 0) return walk_err != kIdxNone ? corrupt(ctx, level, walk_err - start0) : PFSCDC_OK;
   if (nf > 0xffffffffull) return ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "more than 2^32 index entries");
   // ---- the decode: frame starts packed, count pass, prefix sums, fill pass
-  t0 = Clock::now();
+  clk.lap();
   DevMem d_fstart, d_cnt, d_base, d_err;
-  IDX_HIP(ctx, d_fstart.alloc(sizeof(uint64_t) * nf));
-  IDX_HIP(ctx, d_cnt.alloc(sizeof(IdxCount) * nf));
-  IDX_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 2 * (nf + 1)));
-  IDX_HIP(ctx, d_err.alloc(sizeof(uint64_t)));
+  PFS_HIP(ctx, d_fstart.alloc(sizeof(uint64_t) * nf));
+  PFS_HIP(ctx, d_cnt.alloc(sizeof(IdxCount) * nf));
+  PFS_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 2 * (nf + 1)));
+  PFS_HIP(ctx, d_err.alloc(sizeof(uint64_t)));
   uint64_t at = 0;
   for (uint32_t i = 0; i < settled; at += outs[i].count, i++)
     if (outs[i].count)
-      IDX_HIP(ctx, hipMemcpyAsync(d_fstart.as<uint64_t>() + at, d_starts.as<uint64_t>() + walks[i].slot,
+      PFS_HIP(ctx, hipMemcpyAsync(d_fstart.as<uint64_t>() + at, d_starts.as<uint64_t>() + walks[i].slot,
                                   sizeof(uint64_t) * outs[i].count, hipMemcpyDeviceToDevice, s));
   uint64_t h_err = kIdxNone, totals[2] = {0, 0};
-  IDX_HIP(ctx, hipMemcpyAsync(d_err.p, &h_err, sizeof h_err, hipMemcpyHostToDevice, s));
-  IDX_HIP(ctx, launch_index_count(d_buf, n, d_fstart.as<uint64_t>(), nf, d_cnt.as<IdxCount>(),
+  PFS_HIP(ctx, hipMemcpyAsync(d_err.p, &h_err, sizeof h_err, hipMemcpyHostToDevice, s));
+  PFS_HIP(ctx, launch_index_count(d_buf, n, d_fstart.as<uint64_t>(), nf, d_cnt.as<IdxCount>(),
                                   d_err.as<unsigned long long>(), cus, s));
-  IDX_HIP(ctx, launch_index_scan(d_cnt.as<IdxCount>(), nf, d_base.as<uint64_t>(), s));
-  IDX_HIP(ctx, hipMemcpyAsync(&h_err, d_err.p, sizeof h_err, hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 2 * nf, sizeof totals,
+  PFS_HIP(ctx, launch_index_scan(d_cnt.as<IdxCount>(), nf, d_base.as<uint64_t>(), s));
+  PFS_HIP(ctx, hipMemcpyAsync(&h_err, d_err.p, sizeof h_err, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 2 * nf, sizeof totals,
                               hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   h_err = std::min(h_err, walk_err);  // (every settled frame starts in front of walk_err)
   if (h_err != kIdxNone) return corrupt(ctx, level, h_err - start0);
   if (totals[0] > 0xffffffffull) return ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "more than 2^32 DataRefs");
   DevMem d_entries, d_drs, d_blob;
-  IDX_HIP(ctx, d_entries.alloc(sizeof(pfscdc_index_entry) * nf));
-  IDX_HIP(ctx, d_drs.alloc(sizeof(pfscdc_full_dataref) * totals[0]));
-  IDX_HIP(ctx, d_blob.alloc(totals[1]));
-  IDX_HIP(ctx, launch_index_fill(d_buf, n, d_fstart.as<uint64_t>(), nf, d_base.as<uint64_t>(),
+  PFS_HIP(ctx, d_entries.alloc(sizeof(pfscdc_index_entry) * nf));
+  PFS_HIP(ctx, d_drs.alloc(sizeof(pfscdc_full_dataref) * totals[0]));
+  PFS_HIP(ctx, d_blob.alloc(totals[1]));
+  PFS_HIP(ctx, launch_index_fill(d_buf, n, d_fstart.as<uint64_t>(), nf, d_base.as<uint64_t>(),
                                  d_entries.as<pfscdc_index_entry>(),
                                  d_drs.as<pfscdc_full_dataref>(), d_blob.as<char>(), cus, s));
-  IDX_HIP(ctx, hipStreamSynchronize(s));
-  st.ms[3] += ms_since(t0);
+  PFS_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[3] += clk.lap();
   if (keep) {  // a level of File entries only is level 0: its arrays are the resident list
-    t0 = Clock::now();
     DevMem d_flags;
     uint32_t flags[2] = {0, ~0u};  // OR and AND of the entries' flags
-    IDX_HIP(ctx, d_flags.alloc(sizeof flags));
-    IDX_HIP(ctx, hipMemcpyAsync(d_flags.p, flags, sizeof flags, hipMemcpyHostToDevice, s));
-    IDX_HIP(ctx, launch_index_flags(d_entries.as<pfscdc_index_entry>(), nf, d_flags.as<uint32_t>(),
+    PFS_HIP(ctx, d_flags.alloc(sizeof flags));
+    PFS_HIP(ctx, hipMemcpyAsync(d_flags.p, flags, sizeof flags, hipMemcpyHostToDevice, s));
+    PFS_HIP(ctx, launch_index_flags(d_entries.as<pfscdc_index_entry>(), nf, d_flags.as<uint32_t>(),
                                     cus, s));
-    IDX_HIP(ctx, hipMemcpyAsync(flags, d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
-    IDX_HIP(ctx, hipStreamSynchronize(s));
+    PFS_HIP(ctx, hipMemcpyAsync(flags, d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
+    PFS_HIP(ctx, hipStreamSynchronize(s));
     if (!(flags[0] & PFSCDC_IDX_HAS_RANGE)) {
       std::swap(keep->entries, d_entries.p);
       std::swap(keep->drs, d_drs.p);
@@ -218,22 +191,22 @@ int decode_level_device(pfscdc_ctx* ctx, uint32_t level, const uint8_t* d_buf, u
       keep->nb = totals[1];
       *kept = true;
     }
-    st.ms[3] += ms_since(t0);  // the flags pass counts as decode time, kept or not
+    st.ms[3] += clk.lap();  // the flags pass counts as decode time, kept or not
     if (*kept) return PFSCDC_OK;
   }
   // ---- the list to the host
-  t0 = Clock::now();
+  clk.lap();
   out->entries.resize(nf);
   out->drs.resize(totals[0]);
   out->blob.resize(totals[1]);
-  IDX_HIP(ctx, hipMemcpyAsync(out->entries.data(), d_entries.p, sizeof(pfscdc_index_entry) * nf,
+  PFS_HIP(ctx, hipMemcpyAsync(out->entries.data(), d_entries.p, sizeof(pfscdc_index_entry) * nf,
                               hipMemcpyDeviceToHost, s));
   if (totals[0])
-    IDX_HIP(ctx, hipMemcpyAsync(out->drs.data(), d_drs.p, sizeof(pfscdc_full_dataref) * totals[0],
+    PFS_HIP(ctx, hipMemcpyAsync(out->drs.data(), d_drs.p, sizeof(pfscdc_full_dataref) * totals[0],
                                 hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipMemcpyAsync(out->blob.data(), d_blob.p, totals[1], hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipStreamSynchronize(s));
-  st.ms[4] += ms_since(t0);
+  PFS_HIP(ctx, hipMemcpyAsync(out->blob.data(), d_blob.p, totals[1], hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[4] += clk.lap();
   return PFSCDC_OK;
 }
 
@@ -265,9 +238,9 @@ int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const
   if (off[0] < 0 || (uint64_t)off[0] > cb[1])
     return ctx_fail(ctx, PFSCDC_ECORRUPT, "index level " + std::to_string(level) +
                                               ": Range.Offset beyond its chunk");
-  IDX_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
   DevMem d_buf;
-  IDX_HIP(ctx, d_buf.alloc(n + 64));
+  PFS_HIP(ctx, d_buf.alloc(n + 64));
   uint64_t nw = 0;
   int rc = pfscdc_store_read(ctx, store, refs.data(), nc, d_buf.p, n, 1, &nw);
   if (rc == PFSCDC_ENOTFOUND)
@@ -288,15 +261,14 @@ int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const
                                keep, kept);
   // the host arm: the level's bytes to the host, then the specification's decode
   const uint64_t start0 = (uint64_t)off[0];
-  auto t0 = Clock::now();
+  Clock clk;
   std::vector<uint8_t> h(n - start0);
   if (!h.empty())
-    IDX_HIP(ctx, hipMemcpy(h.data(), d_buf.as<uint8_t>() + start0, h.size(), hipMemcpyDeviceToHost));
-  st.ms[4] += ms_since(t0);
-  t0 = Clock::now();
+    PFS_HIP(ctx, hipMemcpy(h.data(), d_buf.as<uint8_t>() + start0, h.size(), hipMemcpyDeviceToHost));
+  st.ms[4] += clk.lap();
   uint64_t err = kIdxNone;
   rc = idx_decode_stream(h.data(), h.size(), h.size(), tail >= 0, out, &err);
-  st.ms[3] += ms_since(t0);
+  st.ms[3] += clk.lap();
   st.n[3] += out->entries.size();
   if (rc == PFSCDC_ECORRUPT) return corrupt(ctx, level, err);
   return rc ? ctx_fail(ctx, rc, "more than 2^32 index records") : PFSCDC_OK;
@@ -304,9 +276,8 @@ int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const
 
 // MergeReader on the device (cdc_kernels.hip §9) over ns streams.  *ran = false: the call
 // belongs to the host arm (a stream out of order, or more than 2^32 - 1 entries or records).
-// Every output array is allocated kMrgGuard bytes longer and the guard, preset to 0xA5, is read
-// back with the list: a kernel that wrote past what the prefix sums counted fails the call.
-constexpr uint64_t kMrgGuard = 64;
+// The output arrays are an OutList's: a kernel that wrote past what the prefix sums counted fails
+// the call.
 
 // One input stream: its three arrays where they lie (host vectors, or a resident list's arrays).
 struct MrgSrc {
@@ -339,102 +310,89 @@ int merge_device(pfscdc_ctx* ctx, int mode, const MrgSrc* src, uint32_t ns, hipM
   if (n == 0) return PFSCDC_OK;
   hipStream_t s = ctx_stream(ctx);
   const int cus = ctx_num_cus(ctx);
-  IDX_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
   // ---- upload: the streams' three arrays, concatenated stream-major
-  auto t0 = Clock::now();
+  Clock clk;
   DevMem d_tab, d_entries, d_blob, d_drs, d_order, d_bad, d_cnt, d_base, d_heads;
-  IDX_HIP(ctx, d_tab.alloc(sizeof(uint64_t) * tab.size()));
-  IDX_HIP(ctx, d_entries.alloc(sizeof(pfscdc_index_entry) * n));
-  IDX_HIP(ctx, d_blob.alloc(nb));
-  IDX_HIP(ctx, d_drs.alloc(sizeof(pfscdc_full_dataref) * nr));
-  IDX_HIP(ctx, d_order.alloc(sizeof(uint32_t) * n));
-  IDX_HIP(ctx, d_bad.alloc(sizeof(uint32_t)));
-  IDX_HIP(ctx, d_heads.alloc(sizeof(uint64_t)));
-  IDX_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * n));
-  IDX_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (n + 1)));
-  IDX_HIP(ctx, hipMemcpyAsync(d_tab.p, tab.data(), sizeof(uint64_t) * tab.size(), hipMemcpyHostToDevice, s));
+  PFS_HIP(ctx, d_tab.alloc(sizeof(uint64_t) * tab.size()));
+  PFS_HIP(ctx, d_entries.alloc(sizeof(pfscdc_index_entry) * n));
+  PFS_HIP(ctx, d_blob.alloc(nb));
+  PFS_HIP(ctx, d_drs.alloc(sizeof(pfscdc_full_dataref) * nr));
+  PFS_HIP(ctx, d_order.alloc(sizeof(uint32_t) * n));
+  PFS_HIP(ctx, d_bad.alloc(sizeof(uint32_t)));
+  PFS_HIP(ctx, d_heads.alloc(sizeof(uint64_t)));
+  PFS_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * n));
+  PFS_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (n + 1)));
+  PFS_HIP(ctx, hipMemcpyAsync(d_tab.p, tab.data(), sizeof(uint64_t) * tab.size(), hipMemcpyHostToDevice, s));
   for (uint32_t k = 0; k < ns; k++) {
     const MrgSrc& l = src[k];
     if (l.n)
-      IDX_HIP(ctx, hipMemcpyAsync(d_entries.as<pfscdc_index_entry>() + sb[k], l.entries,
+      PFS_HIP(ctx, hipMemcpyAsync(d_entries.as<pfscdc_index_entry>() + sb[k], l.entries,
                                   sizeof(pfscdc_index_entry) * l.n, kind, s));
-    if (l.nb) IDX_HIP(ctx, hipMemcpyAsync(d_blob.as<char>() + bb[k], l.blob, l.nb, kind, s));
+    if (l.nb) PFS_HIP(ctx, hipMemcpyAsync(d_blob.as<char>() + bb[k], l.blob, l.nb, kind, s));
     if (l.nr)
-      IDX_HIP(ctx, hipMemcpyAsync(d_drs.as<pfscdc_full_dataref>() + db[k], l.drs,
+      PFS_HIP(ctx, hipMemcpyAsync(d_drs.as<pfscdc_full_dataref>() + db[k], l.drs,
                                   sizeof(pfscdc_full_dataref) * l.nr, kind, s));
   }
-  IDX_HIP(ctx, hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
-  IDX_HIP(ctx, hipStreamSynchronize(s));
-  st.ms[0] = ms_since(t0);
+  PFS_HIP(ctx, hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[0] = clk.lap();
   // ---- rank, then group and count, then the prefix sums
-  t0 = Clock::now();
   const MrgIn in{d_entries.as<pfscdc_index_entry>(), d_blob.as<char>(), d_drs.as<pfscdc_full_dataref>(),
                  d_tab.as<uint64_t>(), d_tab.as<uint64_t>() + ns + 1, d_tab.as<uint64_t>() + 2 * (uint64_t)ns + 1,
                  n, ns, mode};
   uint32_t bad = 0;
-  IDX_HIP(ctx, launch_merge_rank(in, d_order.as<uint32_t>(), d_bad.as<uint32_t>(), cus, s));
-  IDX_HIP(ctx, hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, launch_merge_rank(in, d_order.as<uint32_t>(), d_bad.as<uint32_t>(), cus, s));
+  PFS_HIP(ctx, hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   if (bad) {  // a stream is not strictly ascending: the ranks are no permutation
-    st.ms[1] = ms_since(t0);
+    st.ms[1] = clk.lap();
     *ran = false;
     return PFSCDC_OK;
   }
   uint64_t totals[3] = {0, 0, 0}, heads = 0;
-  IDX_HIP(ctx, hipMemsetAsync(d_heads.p, 0, sizeof(uint64_t), s));
-  IDX_HIP(ctx, launch_merge_group(in, d_order.as<uint32_t>(), d_cnt.as<MrgCount>(),
+  PFS_HIP(ctx, hipMemsetAsync(d_heads.p, 0, sizeof(uint64_t), s));
+  PFS_HIP(ctx, launch_merge_group(in, d_order.as<uint32_t>(), d_cnt.as<MrgCount>(),
                                   d_heads.as<unsigned long long>(), cus, s));
-  IDX_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), n, d_base.as<uint64_t>(), s));
-  IDX_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 3 * n, sizeof totals, hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipMemcpyAsync(&heads, d_heads.p, sizeof heads, hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipStreamSynchronize(s));
-  st.ms[1] = ms_since(t0);
+  PFS_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), n, d_base.as<uint64_t>(), s));
+  PFS_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 3 * n, sizeof totals, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipMemcpyAsync(&heads, d_heads.p, sizeof heads, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[1] = clk.lap();
   if (totals[0] > n || totals[1] > nr || totals[2] > nb)  // (the output is a part of the input)
     return ctx_fail(ctx, PFSCDC_EHIP, "index merge: the counts exceed the input");
   // ---- emit: entries, strings and the copy plan, then the DataRefs
-  t0 = Clock::now();
-  const uint64_t eb = sizeof(pfscdc_index_entry) * totals[0], rb = sizeof(pfscdc_full_dataref) * totals[1];
-  DevMem d_oe, d_ob, d_or, d_copy;
-  IDX_HIP(ctx, d_oe.alloc(eb + kMrgGuard));
-  IDX_HIP(ctx, d_ob.alloc(totals[2] + kMrgGuard));
-  IDX_HIP(ctx, d_or.alloc(rb + kMrgGuard));
-  IDX_HIP(ctx, d_copy.alloc(sizeof(MrgCopy) * n));
-  IDX_HIP(ctx, hipMemsetAsync(d_oe.as<char>() + eb, 0xA5, kMrgGuard, s));
-  IDX_HIP(ctx, hipMemsetAsync(d_ob.as<char>() + totals[2], 0xA5, kMrgGuard, s));
-  IDX_HIP(ctx, hipMemsetAsync(d_or.as<char>() + rb, 0xA5, kMrgGuard, s));
-  IDX_HIP(ctx, hipMemsetAsync(d_copy.p, 0, sizeof(MrgCopy) * n, s));
-  IDX_HIP(ctx, launch_merge_fill(in, d_order.as<uint32_t>(), d_cnt.as<MrgCount>(), d_base.as<uint64_t>(),
-                                 d_oe.as<pfscdc_index_entry>(), d_ob.as<char>(), d_copy.as<MrgCopy>(), cus, s));
-  IDX_HIP(ctx, launch_merge_copy(in, d_copy.as<MrgCopy>(), d_or.as<pfscdc_full_dataref>(), cus, s));
-  IDX_HIP(ctx, hipStreamSynchronize(s));
-  st.ms[2] = ms_since(t0);
+  OutList o;
+  Guards g;
+  DevMem d_copy;
+  PFS_HIP(ctx, o.alloc(totals, s, &g));
+  PFS_HIP(ctx, d_copy.alloc(sizeof(MrgCopy) * n));
+  PFS_HIP(ctx, hipMemsetAsync(d_copy.p, 0, sizeof(MrgCopy) * n, s));
+  PFS_HIP(ctx, launch_merge_fill(in, d_order.as<uint32_t>(), d_cnt.as<MrgCount>(), d_base.as<uint64_t>(),
+                                 o.entries.as<pfscdc_index_entry>(), o.blob.as<char>(),
+                                 d_copy.as<MrgCopy>(), cus, s));
+  PFS_HIP(ctx, launch_list_copy(in.drs, d_copy.as<MrgCopy>(), n, o.drs.as<pfscdc_full_dataref>(),
+                                cus, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[2] = clk.lap();
   // ---- the list to the host
-  t0 = Clock::now();
-  uint8_t guard[3][kMrgGuard];
   if (!keep) {
-    out->entries.resize(totals[0]);
-    out->drs.resize(totals[1]);
-    out->blob.resize(totals[2]);
+    out->entries.resize(o.m);
+    out->drs.resize(o.nr);
+    out->blob.resize(o.nb);
+    if (o.m)
+      PFS_HIP(ctx, hipMemcpyAsync(out->entries.data(), o.entries.p, o.entries.bytes,
+                                  hipMemcpyDeviceToHost, s));
+    if (o.nr)
+      PFS_HIP(ctx, hipMemcpyAsync(out->drs.data(), o.drs.p, o.drs.bytes, hipMemcpyDeviceToHost, s));
+    if (o.nb)
+      PFS_HIP(ctx, hipMemcpyAsync(out->blob.data(), o.blob.p, o.blob.bytes, hipMemcpyDeviceToHost, s));
   }
-  if (!keep && eb) IDX_HIP(ctx, hipMemcpyAsync(out->entries.data(), d_oe.p, eb, hipMemcpyDeviceToHost, s));
-  if (!keep && rb) IDX_HIP(ctx, hipMemcpyAsync(out->drs.data(), d_or.p, rb, hipMemcpyDeviceToHost, s));
-  if (!keep && totals[2]) IDX_HIP(ctx, hipMemcpyAsync(out->blob.data(), d_ob.p, totals[2], hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipMemcpyAsync(guard[0], d_oe.as<char>() + eb, kMrgGuard, hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipMemcpyAsync(guard[1], d_ob.as<char>() + totals[2], kMrgGuard, hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipMemcpyAsync(guard[2], d_or.as<char>() + rb, kMrgGuard, hipMemcpyDeviceToHost, s));
-  IDX_HIP(ctx, hipStreamSynchronize(s));
-  st.ms[3] = ms_since(t0);
-  for (auto& g : guard)
-    for (uint8_t b : g)
-      if (b != 0xA5) return ctx_fail(ctx, PFSCDC_EHIP, "index merge: a kernel wrote past its array");
-  if (keep) {
-    std::swap(keep->entries, d_oe.p);
-    std::swap(keep->drs, d_or.p);
-    std::swap(keep->blob, d_ob.p);
-    keep->n = totals[0];
-    keep->nr = totals[1];
-    keep->nb = totals[2];
-  }
+  PFS_HIP(ctx, g.fetch(s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
+  st.ms[3] = clk.lap();
+  if (!g.ok()) return ctx_fail(ctx, PFSCDC_EHIP, "index merge: a kernel wrote past its array");
+  if (keep) o.release(ctx, keep);
   st.n[2] = heads;
   st.n[3] = totals[0];
   return PFSCDC_OK;
@@ -511,10 +469,10 @@ int pfscdc_index_merge_ctx(pfscdc_ctx* ctx, int mode, const pfscdc_index_list* c
   }
   uint64_t n_in = 0;
   for (uint32_t k = 0; k < ns; k++) n_in += lists[k] ? lists[k]->entries.size() : 0;
-  auto t0 = Clock::now();
+  pfscdc::Clock clk;
   const int rc = mode == PFSCDC_MERGE_FILES ? pfscdc_index_merge(lists, nfilesets, out)
                                             : pfscdc_index_merge_deletive(lists, nfilesets, out);
-  st.ms[1] += ms_since(t0);
+  st.ms[1] += clk.lap();
   st.n[0] = 0;
   st.n[1] = n_in;
   st.n[3] = *out ? (*out)->entries.size() : 0;
@@ -569,8 +527,7 @@ int pfscdc_index_read_dev(pfscdc_ctx* ctx, const pfscdc_store* store, const void
   }
   // the host path's list, uploaded
   if (int rc = pfscdc::dev_list_upload(ctx, *result, out)) return rc;
-  rs.n[1] = sizeof(pfscdc_index_entry) * result->entries.size() +
-            sizeof(pfscdc_full_dataref) * result->drs.size() + result->blob.size();
+  rs.n[1] = pfscdc::list_bytes(*result);
   return PFSCDC_OK;
 }
 
@@ -604,28 +561,26 @@ int pfscdc_index_merge_dev(pfscdc_ctx* ctx, int mode, const pfscdc_dev_list* con
   const float ms_rank = st.ms[1];
   std::vector<std::unique_ptr<List>> own(ns);
   std::vector<const List*> hl(ns, nullptr);
-  auto t0 = Clock::now();
+  pfscdc::Clock clk;
   for (uint32_t k = 0; k < ns; k++) {
     if (!lists[k]) continue;
     own[k].reset(new List());
     if (int rc = pfscdc::dev_list_download(ctx, *lists[k], own[k].get())) return rc;
     hl[k] = own[k].get();
   }
-  const float ms_down = ms_since(t0);
-  t0 = Clock::now();
+  const float ms_down = clk.lap();
   pfscdc_index_list* merged = nullptr;
   int rc = mode == PFSCDC_MERGE_FILES ? pfscdc_index_merge(hl.data(), nfilesets, &merged)
                                       : pfscdc_index_merge_deletive(hl.data(), nfilesets, &merged);
   std::unique_ptr<List> m(merged);
   if (rc) return pfscdc::ctx_fail(ctx, rc, "index merge: more than 2^32 - 1 records in the merged list");
-  const float ms_host = ms_since(t0);
-  t0 = Clock::now();
+  const float ms_host = clk.lap();
   rc = pfscdc::dev_list_upload(ctx, *m, out);
   const uint64_t n_in = st.n[1];
   st = MergeStats();
   st.n[1] = n_in;
   st.n[3] = m->entries.size();
-  st.ms[0] = ms_since(t0);
+  st.ms[0] = clk.lap();
   st.ms[1] = ms_rank + ms_host;
   st.ms[3] = ms_down;
   return rc;

@@ -172,9 +172,9 @@ struct pfscdc_ctx {
   IndexStats index_stats;             // the last pfscdc_index_read
   MergeStats merge_stats;             // the last pfscdc_index_merge_ctx
   ResidentStats resident_stats;       // the last calls over device-resident lists
-  SourceStats source_stats;           // the last pfscdc_source_open
-  DiffStats diff_stats;               // the last pfscdc_source_diff
-  CopyMapStats copy_map_stats;        // the last pfscdc_dev_list_copy_map
+  PassStats source_stats;             // the last pfscdc_source_open
+  PassStats diff_stats;               // the last pfscdc_source_diff
+  PassStats copy_map_stats;           // the last pfscdc_dev_list_copy_map
 };
 
 namespace pfscdc {
@@ -182,9 +182,9 @@ const pfscdc_params& ctx_params(const pfscdc_ctx* ctx) { return ctx->params; }
 IndexStats& ctx_index_stats(pfscdc_ctx* ctx) { return ctx->index_stats; }
 MergeStats& ctx_merge_stats(pfscdc_ctx* ctx) { return ctx->merge_stats; }
 ResidentStats& ctx_resident_stats(pfscdc_ctx* ctx) { return ctx->resident_stats; }
-SourceStats& ctx_source_stats(pfscdc_ctx* ctx) { return ctx->source_stats; }
-DiffStats& ctx_diff_stats(pfscdc_ctx* ctx) { return ctx->diff_stats; }
-CopyMapStats& ctx_copy_map_stats(pfscdc_ctx* ctx) { return ctx->copy_map_stats; }
+PassStats& ctx_source_stats(pfscdc_ctx* ctx) { return ctx->source_stats; }
+PassStats& ctx_diff_stats(pfscdc_ctx* ctx) { return ctx->diff_stats; }
+PassStats& ctx_copy_map_stats(pfscdc_ctx* ctx) { return ctx->copy_map_stats; }
 int ctx_num_cus(const pfscdc_ctx* ctx) { return ctx->num_cus; }
 }  // namespace pfscdc
 

@@ -360,16 +360,21 @@ hipError_t launch_merge_rank(const MrgIn& in, uint32_t* order, uint32_t* bad, in
 // before) += the groups
 hipError_t launch_merge_group(const MrgIn& in, const uint32_t* order, MrgCount* cnt,
                               unsigned long long* heads, int num_cus, hipStream_t st);
-// exclusive prefix sums of cnt[0, n) into base[0, n]: {entries, records, blob bytes} each
+// The list passes (merge, Source, diff, copy map) share one contract.  A count kernel gives
+// cnt[i] = {entries, DataRefs, blob bytes} item i emits; launch_merge_scan turns cnt[0, n) into
+// exclusive prefix sums base[0, n], three per item, the totals last.  A fill kernel then writes
+// item i's entries from entries[base[3i]] and their strings from blob + base[3i + 2], and only if
+// what it counts again equals its ranges base[3i + 3 ...] - base[3i ...]; into copy[] (zeroed
+// before) it puts the source entries whose DataRefs go to drs[base[3i + 1], ...), and
+// launch_list_copy moves those.
 hipError_t launch_merge_scan(const MrgCount* cnt, uint64_t n, uint64_t* base, hipStream_t st);
-// entries[base[3p]], its strings at blob + base[3p + 2], and copy[] (zeroed before) for the
-// source entries whose DataRefs go to drs[base[3p + 1], ...)
+// the merged entries and their strings, copy[] (the contract above, p a merged position)
 hipError_t launch_merge_fill(const MrgIn& in, const uint32_t* order, const MrgCount* cnt,
                              const uint64_t* base, pfscdc_index_entry* entries, char* blob,
                              MrgCopy* copy, int num_cus, hipStream_t st);
-// the DataRefs copy[] names, 16 bytes per lane
-hipError_t launch_merge_copy(const MrgIn& in, const MrgCopy* copy, pfscdc_full_dataref* drs,
-                             int num_cus, hipStream_t st);
+// dst[copy[i].dst ...] = src[copy[i].src ...] for each of the n source entries, 16 bytes per lane
+hipError_t launch_list_copy(const pfscdc_full_dataref* src, const MrgCopy* copy, uint64_t n,
+                            pfscdc_full_dataref* dst, int num_cus, hipStream_t st);
 // what pfscdc_last_merge_stats / pfscdc_last_merge_timings report
 struct MergeStats {
   uint64_t n[4] = {};
@@ -477,10 +482,9 @@ struct SrcMeta {  // per output entry
 // cnt[i] = {entries, DataRefs, blob bytes} input entry i emits; *bad |= SrcBad (zeroed before)
 hipError_t launch_src_count(const RtarList& in, const SrcPred& pr, MrgCount* cnt, uint32_t* bad,
                             int num_cus, hipStream_t st);
-// after launch_merge_scan of cnt into base: the output entries, their strings, meta (end unset),
-// the infos' type, flags and file size, sizes[o] = {0, 0, file size}, maxdepth[0] and the
-// directories inserted in maxdepth[1] (both zeroed before),
-// copy[] (zeroed before) and through it the selected files' DataRefs into drs
+// the output entries, their strings and through copy[] the selected files' DataRefs into drs (the
+// list passes' contract); meta (end unset), the infos' type, flags and file size, sizes[o] =
+// {0, 0, file size}, maxdepth[0] and the directories inserted in maxdepth[1] (both zeroed before)
 hipError_t launch_src_fill(const RtarList& in, const SrcPred& pr, const MrgCount* cnt,
                            const uint64_t* base, pfscdc_index_entry* entries, char* blob,
                            MrgCopy* copy, SrcMeta* meta, pfscdc_file_info* infos, MrgCount* sizes,
@@ -506,12 +510,12 @@ hipError_t launch_src_level_gather(const SrcMeta* meta, const pfscdc_file_info* 
 hipError_t launch_src_scatter(const SrcMeta* meta, const uint64_t* base, const pfscdc_segment* segs,
                               uint64_t n, int level, pfscdc_file_info* infos, int num_cus,
                               hipStream_t st);
-// what pfscdc_last_source_stats / pfscdc_last_source_timings report
-struct SourceStats {
+// what pfscdc_last_{source,diff,copy_map}_stats / _timings report
+struct PassStats {
   uint64_t n[8] = {};
   float ms[4] = {};
 };
-SourceStats& ctx_source_stats(pfscdc_ctx* ctx);
+PassStats& ctx_source_stats(pfscdc_ctx* ctx);
 
 // ---- DiffFile on the device (diff_dev.cpp; kernels in cdc_kernels.hip §12) ----
 struct DiffSide {  // a Source: its list and one info per entry
@@ -531,18 +535,13 @@ hipError_t launch_diff_rank(const DiffSide& a, const DiffSide& b, DiffRank* rank
 hipError_t launch_diff_fill(uint64_t na, uint64_t nb, const DiffRank* rank, const MrgCount* sel,
                             const uint64_t* base_a, const MrgCount* emit_b, const uint64_t* base_e,
                             pfscdc_diff_pair* pairs, uint64_t npairs, int num_cus, hipStream_t st);
-// after launch_merge_scan of a side's sel into base: its selected entries, strings and infos,
-// copy[] (zeroed before) and through it their DataRefs into drs
+// a side's selected entries, their strings and infos, and through copy[] their DataRefs into drs
+// (the list passes' contract, sel the counts)
 hipError_t launch_diff_select(const DiffSide& in, const MrgCount* sel, const uint64_t* base,
                               pfscdc_index_entry* entries, char* blob, MrgCopy* copy,
                               pfscdc_file_info* infos, pfscdc_full_dataref* drs, int num_cus,
                               hipStream_t st);
-// what pfscdc_last_diff_stats / pfscdc_last_diff_timings report
-struct DiffStats {
-  uint64_t n[8] = {};
-  float ms[4] = {};
-};
-DiffStats& ctx_diff_stats(pfscdc_ctx* ctx);
+PassStats& ctx_diff_stats(pfscdc_ctx* ctx);
 
 // ---- CopyFile's selection and path transform (copy_map_dev.cpp; kernels in cdc_kernels.hip §13) ----
 struct CmapPred {  // CopyArg (copy_map.h) with its strings on the device
@@ -554,20 +553,11 @@ struct CmapPred {  // CopyArg (copy_map.h) with its strings on the device
 // path that is not IsClean(p, false) or whose new path exceeds 2^32 - 1 bytes
 hipError_t launch_cmap_count(const RtarList& in, const CmapPred& pr, MrgCount* cnt, uint32_t* bad,
                              int num_cus, hipStream_t st);
-// after launch_merge_scan of cnt into base: the selected entries with their new paths and tags,
-// and copy[] (zeroed before) for launch_cmap_copy
+// the selected entries with their new paths and tags, copy[] (the list passes' contract)
 hipError_t launch_cmap_fill(const RtarList& in, const CmapPred& pr, const MrgCount* cnt,
                             const uint64_t* base, pfscdc_index_entry* entries, char* blob,
                             MrgCopy* copy, int num_cus, hipStream_t st);
-// the DataRefs copy[] names (merge_copy_kernel over a single list)
-hipError_t launch_cmap_copy(const RtarList& in, const MrgCopy* copy, pfscdc_full_dataref* drs,
-                            int num_cus, hipStream_t st);
-// what pfscdc_last_copy_map_stats / pfscdc_last_copy_map_timings report
-struct CopyMapStats {
-  uint64_t n[8] = {};
-  float ms[4] = {};
-};
-CopyMapStats& ctx_copy_map_stats(pfscdc_ctx* ctx);
+PassStats& ctx_copy_map_stats(pfscdc_ctx* ctx);
 
 hipError_t launch_synth(uint8_t* out, const uint64_t* offs, uint32_t nfiles, const uint32_t* ids,
                         const uint64_t* starts, uint64_t seed, uint32_t mode, hipStream_t st);

@@ -2,14 +2,13 @@
 // and from the host, and GetFileTAR over it (the plan and window stages of tar_plan as kernels,
 // cdc_kernels.hip §10; the read path's sibling read_slices_dev_impl is in pfscdc.cpp, the
 // batch of the runs' chunks beside StoreBatch in writer.cpp).
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "dev_list.h"
-#include "index_list.h"
-#include "pfscdc_internal.h"
+#include "dev_pass.h"
 
 pfscdc_dev_list::~pfscdc_dev_list() {
   for (void* p : {entries, blob, drs, dpre, ent, off})
@@ -21,19 +20,6 @@ namespace {
 using namespace pfscdc;
 using List = pfscdc_index_list;
 
-#define RES_HIP(ctx, expr)                                                             \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return pfscdc::ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PFSCDC_ENOMEM : PFSCDC_EHIP, \
-                              std::string(#expr) + ": " + hipGetErrorString(e_));      \
-  } while (0)
-
-RtarList view(const pfscdc_dev_list& d) {
-  return RtarList{(const pfscdc_index_entry*)d.entries, (const char*)d.blob,
-                  (const pfscdc_full_dataref*)d.drs, d.n, d.nr, d.nb};
-}
-
 int check_handle(pfscdc_ctx* ctx, const pfscdc_dev_list* d) {
   if (d->device != ctx_device(ctx))
     return ctx_fail(ctx, PFSCDC_EINVAL, "a resident list of another device");
@@ -44,15 +30,15 @@ int check_handle(pfscdc_ctx* ctx, const pfscdc_dev_list* d) {
 int fetch_path(pfscdc_ctx* ctx, const pfscdc_dev_list& d, uint64_t i, std::string* path) {
   hipStream_t s = ctx_stream(ctx);
   pfscdc_index_entry e;
-  RES_HIP(ctx, hipMemcpyAsync(&e, (const pfscdc_index_entry*)d.entries + i, sizeof e,
+  PFS_HIP(ctx, hipMemcpyAsync(&e, (const pfscdc_index_entry*)d.entries + i, sizeof e,
                               hipMemcpyDeviceToHost, s));
-  RES_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   path->clear();
   if (e.path_off <= d.nb && e.path_len <= d.nb - e.path_off && e.path_len) {
     path->resize(e.path_len);
-    RES_HIP(ctx, hipMemcpyAsync(&(*path)[0], (const char*)d.blob + e.path_off, e.path_len,
+    PFS_HIP(ctx, hipMemcpyAsync(&(*path)[0], (const char*)d.blob + e.path_off, e.path_len,
                                 hipMemcpyDeviceToHost, s));
-    RES_HIP(ctx, hipStreamSynchronize(s));
+    PFS_HIP(ctx, hipStreamSynchronize(s));
     path->resize(std::strlen(path->c_str()));  // as the host reads it: up to the first NUL
   }
   return PFSCDC_OK;
@@ -71,45 +57,45 @@ int plan(pfscdc_ctx* ctx, pfscdc_dev_list* d) {
   };
   if (d->nb >= (1ull << 32))
     return done(PFSCDC_EUNSUPPORTED, "a resident list's strings of 4 GiB or more as a tar name table");
-  RES_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
   hipStream_t s = ctx_stream(ctx);
   const int cus = ctx_num_cus(ctx);
   const RtarList l = view(*d);
   GuardMem dsz, dpre, ent, span, off, flags;
   Guards g;
-  RES_HIP(ctx, dsz.alloc(sizeof(uint64_t) * l.nr, s));
-  RES_HIP(ctx, dpre.alloc(sizeof(uint64_t) * (l.nr + 1), s));
-  RES_HIP(ctx, ent.alloc(sizeof(TarEntry) * l.n, s));
-  RES_HIP(ctx, span.alloc(sizeof(uint64_t) * l.n, s));
-  RES_HIP(ctx, off.alloc(sizeof(uint64_t) * (l.n + 1), s));
-  RES_HIP(ctx, flags.alloc(16, s));
+  PFS_HIP(ctx, dsz.alloc(sizeof(uint64_t) * l.nr, s));
+  PFS_HIP(ctx, dpre.alloc(sizeof(uint64_t) * (l.nr + 1), s));
+  PFS_HIP(ctx, ent.alloc(sizeof(TarEntry) * l.n, s));
+  PFS_HIP(ctx, span.alloc(sizeof(uint64_t) * l.n, s));
+  PFS_HIP(ctx, off.alloc(sizeof(uint64_t) * (l.n + 1), s));
+  PFS_HIP(ctx, flags.alloc(16, s));
   for (const GuardMem* m : {&dsz, &dpre, &ent, &span, &off, &flags}) g.add(*m);
   struct {
     unsigned long long err;
     uint32_t bad, pad;
   } h{kRtarNoErr, 0, 0};
-  RES_HIP(ctx, hipMemcpyAsync(flags.p, &h, sizeof h, hipMemcpyHostToDevice, s));
-  RES_HIP(ctx, launch_rtar_sizes(l.drs, l.nr, dsz.as<uint64_t>(), flags.as<uint32_t>() + 2, cus, s));
-  RES_HIP(ctx, launch_rtar_scan(dsz.as<uint64_t>(), l.nr, dpre.as<uint64_t>(), nullptr, s));
-  RES_HIP(ctx, launch_rtar_entries(l, dpre.as<uint64_t>(), ent.as<TarEntry>(), span.as<uint64_t>(),
+  PFS_HIP(ctx, hipMemcpyAsync(flags.p, &h, sizeof h, hipMemcpyHostToDevice, s));
+  PFS_HIP(ctx, launch_rtar_sizes(l.drs, l.nr, dsz.as<uint64_t>(), flags.as<uint32_t>() + 2, cus, s));
+  PFS_HIP(ctx, launch_rtar_scan(dsz.as<uint64_t>(), l.nr, dpre.as<uint64_t>(), nullptr, s));
+  PFS_HIP(ctx, launch_rtar_entries(l, dpre.as<uint64_t>(), ent.as<TarEntry>(), span.as<uint64_t>(),
                                    flags.as<unsigned long long>(), cus, s));
-  RES_HIP(ctx, launch_rtar_scan(span.as<uint64_t>(), l.n, off.as<uint64_t>(), ent.as<TarEntry>(), s));
+  PFS_HIP(ctx, launch_rtar_scan(span.as<uint64_t>(), l.n, off.as<uint64_t>(), ent.as<TarEntry>(), s));
   uint64_t at = 0;
-  RES_HIP(ctx, hipMemcpyAsync(&h, flags.p, sizeof h, hipMemcpyDeviceToHost, s));
-  RES_HIP(ctx, hipMemcpyAsync(&at, off.as<uint64_t>() + l.n, sizeof at, hipMemcpyDeviceToHost, s));
-  RES_HIP(ctx, g.fetch(s));
-  RES_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, hipMemcpyAsync(&h, flags.p, sizeof h, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipMemcpyAsync(&at, off.as<uint64_t>() + l.n, sizeof at, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, g.fetch(s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   if (!g.ok()) return ctx_fail(ctx, PFSCDC_EHIP, "tar plan: a kernel wrote past its array");
   if (h.bad) return done(PFSCDC_EINVAL, "a DataRef reaches past its chunk");
   uint64_t over = ~0ull;  // the entry at which the offsets pass 2^62
   if (at > (1ull << 62)) {
     // the first i with off[i] > 2^62: entry i - 1 is where tar_plan's running offset passes it
     GuardMem w;
-    RES_HIP(ctx, w.alloc(sizeof(RtarWindow), s));
+    PFS_HIP(ctx, w.alloc(sizeof(RtarWindow), s));
     RtarWindow hw;
-    RES_HIP(ctx, launch_rtar_window(l, off.as<uint64_t>(), 1ull << 62, ~0ull, w.as<RtarWindow>(), s));
-    RES_HIP(ctx, hipMemcpyAsync(&hw, w.p, sizeof hw, hipMemcpyDeviceToHost, s));
-    RES_HIP(ctx, hipStreamSynchronize(s));
+    PFS_HIP(ctx, launch_rtar_window(l, off.as<uint64_t>(), 1ull << 62, ~0ull, w.as<RtarWindow>(), s));
+    PFS_HIP(ctx, hipMemcpyAsync(&hw, w.p, sizeof hw, hipMemcpyDeviceToHost, s));
+    PFS_HIP(ctx, hipStreamSynchronize(s));
     over = hw.i0;  // the last entry whose offset is still <= 2^62
   }
   if (h.err != kRtarNoErr && (h.err >> 8) <= over) {
@@ -159,39 +145,93 @@ int dev_list_upload(pfscdc_ctx* ctx, const pfscdc_index_list& l, pfscdc_dev_list
   if (l.entries.size() > 0xffffffffull || l.drs.size() > 0xffffffffull)
     return ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "more than 2^32 - 1 records in a resident list");
   std::unique_ptr<pfscdc_dev_list> d(dev_list_new(ctx));
-  RES_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
   hipStream_t s = ctx_stream(ctx);
   d->n = l.entries.size();
   d->nr = l.drs.size();
   d->nb = l.blob.size();
   const uint64_t eb = sizeof(pfscdc_index_entry) * d->n, rb = sizeof(pfscdc_full_dataref) * d->nr;
-  RES_HIP(ctx, hipMalloc(&d->entries, eb + kGuard));
-  RES_HIP(ctx, hipMalloc(&d->drs, rb + kGuard));
-  RES_HIP(ctx, hipMalloc(&d->blob, d->nb + kGuard));
-  if (eb) RES_HIP(ctx, hipMemcpyAsync(d->entries, l.entries.data(), eb, hipMemcpyHostToDevice, s));
-  if (rb) RES_HIP(ctx, hipMemcpyAsync(d->drs, l.drs.data(), rb, hipMemcpyHostToDevice, s));
-  if (d->nb) RES_HIP(ctx, hipMemcpyAsync(d->blob, l.blob.data(), d->nb, hipMemcpyHostToDevice, s));
-  RES_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, hipMalloc(&d->entries, eb + kGuard));
+  PFS_HIP(ctx, hipMalloc(&d->drs, rb + kGuard));
+  PFS_HIP(ctx, hipMalloc(&d->blob, d->nb + kGuard));
+  if (eb) PFS_HIP(ctx, hipMemcpyAsync(d->entries, l.entries.data(), eb, hipMemcpyHostToDevice, s));
+  if (rb) PFS_HIP(ctx, hipMemcpyAsync(d->drs, l.drs.data(), rb, hipMemcpyHostToDevice, s));
+  if (d->nb) PFS_HIP(ctx, hipMemcpyAsync(d->blob, l.blob.data(), d->nb, hipMemcpyHostToDevice, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   *out = d.release();
   return PFSCDC_OK;
 }
 
 int dev_list_download(pfscdc_ctx* ctx, const pfscdc_dev_list& d, pfscdc_index_list* out) {
   if (int rc = check_handle(ctx, &d)) return rc;
-  RES_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
   hipStream_t s = ctx_stream(ctx);
   out->entries.resize(d.n);
   out->drs.resize(d.nr);
   out->blob.resize(d.nb);
   out->tar.clear();
   if (d.n)
-    RES_HIP(ctx, hipMemcpyAsync(out->entries.data(), d.entries, sizeof(pfscdc_index_entry) * d.n,
+    PFS_HIP(ctx, hipMemcpyAsync(out->entries.data(), d.entries, sizeof(pfscdc_index_entry) * d.n,
                                 hipMemcpyDeviceToHost, s));
   if (d.nr)
-    RES_HIP(ctx, hipMemcpyAsync(out->drs.data(), d.drs, sizeof(pfscdc_full_dataref) * d.nr,
+    PFS_HIP(ctx, hipMemcpyAsync(out->drs.data(), d.drs, sizeof(pfscdc_full_dataref) * d.nr,
                                 hipMemcpyDeviceToHost, s));
-  if (d.nb) RES_HIP(ctx, hipMemcpyAsync(out->blob.data(), d.blob, d.nb, hipMemcpyDeviceToHost, s));
-  RES_HIP(ctx, hipStreamSynchronize(s));
+  if (d.nb) PFS_HIP(ctx, hipMemcpyAsync(out->blob.data(), d.blob, d.nb, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
+  return PFSCDC_OK;
+}
+
+hipError_t OutList::alloc(const uint64_t totals[3], hipStream_t s, Guards* g) {
+  m = totals[0];
+  nr = totals[1];
+  nb = totals[2];
+  const struct {
+    GuardMem* mem;
+    uint64_t bytes;
+  } want[] = {{&entries, sizeof(pfscdc_index_entry) * m},
+              {&blob, nb},
+              {&drs, sizeof(pfscdc_full_dataref) * nr}};
+  for (const auto& w : want) {
+    if (hipError_t e = w.mem->alloc(w.bytes, s)) return e;
+    g->add(*w.mem);
+  }
+  return hipSuccess;
+}
+
+pfscdc_dev_list* OutList::release(pfscdc_ctx* ctx, pfscdc_dev_list* keep) {
+  pfscdc_dev_list* d = keep ? keep : dev_list_new(ctx);
+  std::swap(d->entries, entries.p);  // (what keep held before goes with this OutList)
+  std::swap(d->blob, blob.p);
+  std::swap(d->drs, drs.p);
+  d->n = m;
+  d->nr = nr;
+  d->nb = nb;
+  return d;
+}
+
+pfscdc_source* source_new(pfscdc_ctx* ctx, OutList* o, GuardMem* infos) {
+  pfscdc_source* src = new pfscdc_source();
+  src->device = ctx_device(ctx);
+  src->list = o->release(ctx);
+  src->infos = infos->release();
+  return src;
+}
+
+int source_upload(pfscdc_ctx* ctx, const pfscdc_index_list& l,
+                  const std::vector<pfscdc_file_info>& infos, pfscdc_source** out, uint64_t* bytes) {
+  std::unique_ptr<pfscdc_source> src(new pfscdc_source());
+  src->device = ctx_device(ctx);
+  if (int rc = dev_list_upload(ctx, l, &src->list)) return rc;
+  *bytes += list_bytes(l);
+  const uint64_t ib = sizeof(pfscdc_file_info) * infos.size();
+  PFS_HIP(ctx, hipMalloc(&src->infos, ib + kGuard));
+  if (ib) {
+    hipStream_t s = ctx_stream(ctx);
+    PFS_HIP(ctx, hipMemcpyAsync(src->infos, infos.data(), ib, hipMemcpyHostToDevice, s));
+    PFS_HIP(ctx, hipStreamSynchronize(s));
+    *bytes += ib;
+  }
+  *out = src.release();
   return PFSCDC_OK;
 }
 
@@ -233,9 +273,9 @@ int pfscdc_dev_list_tar_layout(pfscdc_ctx* ctx, pfscdc_dev_list* d, uint64_t* to
   *total = d->total;
   if (entry_offsets) {
     hipStream_t s = ctx_stream(ctx);
-    RES_HIP(ctx, hipMemcpyAsync(entry_offsets, d->off, sizeof(uint64_t) * (d->n + 1),
+    PFS_HIP(ctx, hipMemcpyAsync(entry_offsets, d->off, sizeof(uint64_t) * (d->n + 1),
                                 hipMemcpyDeviceToHost, s));
-    RES_HIP(ctx, hipStreamSynchronize(s));
+    PFS_HIP(ctx, hipStreamSynchronize(s));
   }
   return PFSCDC_OK;
 }
@@ -260,7 +300,7 @@ int pfscdc_dev_list_read_tar(pfscdc_ctx* ctx, const pfscdc_store* store, pfscdc_
   if (window > out_cap || (window && !out))
     return ctx_fail(ctx, PFSCDC_EINVAL, "out_cap below the window's bytes");
   if (window == 0) return PFSCDC_OK;
-  RES_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
   hipStream_t s = ctx_stream(ctx);
   const int cus = ctx_num_cus(ctx);
   const RtarList l = view(*d);
@@ -268,11 +308,11 @@ int pfscdc_dev_list_read_tar(pfscdc_ctx* ctx, const pfscdc_store* store, pfscdc_
   GuardMem d_w, d_cnt, d_base, d_slices, d_out_off, d_blk, d_runs;
   Guards g;
   RtarWindow w;
-  RES_HIP(ctx, d_w.alloc(sizeof(RtarWindow), s));
+  PFS_HIP(ctx, d_w.alloc(sizeof(RtarWindow), s));
   g.add(d_w);
-  RES_HIP(ctx, launch_rtar_window(l, (const uint64_t*)d->off, begin, end, d_w.as<RtarWindow>(), s));
-  RES_HIP(ctx, hipMemcpyAsync(&w, d_w.p, sizeof w, hipMemcpyDeviceToHost, s));
-  RES_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, launch_rtar_window(l, (const uint64_t*)d->off, begin, end, d_w.as<RtarWindow>(), s));
+  PFS_HIP(ctx, hipMemcpyAsync(&w, d_w.p, sizeof w, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   rs.n[5] += sizeof w;
   if (w.i0 > w.i1 || w.i1 > l.n || w.k0 > w.k1 || w.k1 > l.nr)
     return ctx_fail(ctx, PFSCDC_EHIP, "tar window: the search left the list");
@@ -280,43 +320,43 @@ int pfscdc_dev_list_read_tar(pfscdc_ctx* ctx, const pfscdc_store* store, pfscdc_
   const uint64_t nk = w.k1 - w.k0;
   const RtarPieces pc{l, (const uint64_t*)d->dpre, (const TarEntry*)d->ent, w, begin, end};
   uint64_t totals[3] = {0, 0, 0};  // pieces, runs, keystream blocks
-  RES_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * nk, s));
-  RES_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (nk + 1), s));
+  PFS_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * nk, s));
+  PFS_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (nk + 1), s));
   g.add(d_cnt);
   g.add(d_base);
   if (nk) {
-    RES_HIP(ctx, launch_rtar_pieces(pc, d_cnt.as<MrgCount>(), nullptr, nullptr, nullptr, nullptr,
+    PFS_HIP(ctx, launch_rtar_pieces(pc, d_cnt.as<MrgCount>(), nullptr, nullptr, nullptr, nullptr,
                                     nullptr, cus, s));
-    RES_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), nk, d_base.as<uint64_t>(), s));
-    RES_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 3 * nk, sizeof totals,
+    PFS_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), nk, d_base.as<uint64_t>(), s));
+    PFS_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 3 * nk, sizeof totals,
                                 hipMemcpyDeviceToHost, s));
-    RES_HIP(ctx, hipStreamSynchronize(s));
+    PFS_HIP(ctx, hipStreamSynchronize(s));
     rs.n[5] += sizeof totals;
   }
   const uint64_t m = totals[0], nruns = totals[1], nblocks = totals[2];
   if (m > nk || nruns > m || m > 0xffffffffull)
     return ctx_fail(ctx, PFSCDC_EHIP, "tar window: the counts exceed the input");
-  RES_HIP(ctx, d_slices.alloc(sizeof(pfscdc_slice) * m, s));
-  RES_HIP(ctx, d_out_off.alloc(sizeof(uint64_t) * (m + 1), s));
-  RES_HIP(ctx, d_blk.alloc(sizeof(uint64_t) * (m + 1), s));
-  RES_HIP(ctx, d_runs.alloc(sizeof(RtarRun) * nruns, s));
+  PFS_HIP(ctx, d_slices.alloc(sizeof(pfscdc_slice) * m, s));
+  PFS_HIP(ctx, d_out_off.alloc(sizeof(uint64_t) * (m + 1), s));
+  PFS_HIP(ctx, d_blk.alloc(sizeof(uint64_t) * (m + 1), s));
+  PFS_HIP(ctx, d_runs.alloc(sizeof(RtarRun) * nruns, s));
   for (const GuardMem* x : {&d_slices, &d_out_off, &d_blk, &d_runs}) g.add(*x);
   std::vector<RtarRun> runs(nruns);
   if (m) {
-    RES_HIP(ctx, launch_rtar_pieces(pc, d_cnt.as<MrgCount>(), d_base.as<uint64_t>(),
+    PFS_HIP(ctx, launch_rtar_pieces(pc, d_cnt.as<MrgCount>(), d_base.as<uint64_t>(),
                                     d_slices.as<pfscdc_slice>(), d_out_off.as<uint64_t>(),
                                     d_blk.as<uint64_t>(), d_runs.as<RtarRun>(), cus, s));
-    RES_HIP(ctx, hipMemcpyAsync(runs.data(), d_runs.p, sizeof(RtarRun) * nruns,
+    PFS_HIP(ctx, hipMemcpyAsync(runs.data(), d_runs.p, sizeof(RtarRun) * nruns,
                                 hipMemcpyDeviceToHost, s));
     rs.n[5] += sizeof(RtarRun) * nruns;
   } else {
     const uint64_t zero[1] = {0};  // the arrays' one entry each: no pieces, no blocks
-    RES_HIP(ctx, hipMemcpyAsync(d_out_off.p, zero, sizeof zero, hipMemcpyHostToDevice, s));
-    RES_HIP(ctx, hipMemcpyAsync(d_blk.p, zero, sizeof zero, hipMemcpyHostToDevice, s));
+    PFS_HIP(ctx, hipMemcpyAsync(d_out_off.p, zero, sizeof zero, hipMemcpyHostToDevice, s));
+    PFS_HIP(ctx, hipMemcpyAsync(d_blk.p, zero, sizeof zero, hipMemcpyHostToDevice, s));
     rs.n[6] += 2 * sizeof zero;
   }
-  RES_HIP(ctx, g.fetch(s));
-  RES_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, g.fetch(s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   rs.n[5] += g.host.size();
   if (!g.ok()) return ctx_fail(ctx, PFSCDC_EHIP, "tar window: a kernel wrote past its array");
   // ---- the runs' chunks: looked up and deduplicated on the host, one number per run back
@@ -331,21 +371,21 @@ int pfscdc_dev_list_read_tar(pfscdc_ctx* ctx, const pfscdc_store* store, pfscdc_
   // the run -> chunk table and the chunks' stored offsets; the kernel that sets slice.chunk also
   // holds every slice against its chunk's stored length, since the gather checks nothing
   GuardMem d_table, d_coffs, d_bad;
-  RES_HIP(ctx, d_table.alloc(sizeof(uint32_t) * nruns, s));
-  RES_HIP(ctx, d_coffs.alloc(sizeof(uint64_t) * (nchunks + 1), s));
-  RES_HIP(ctx, d_bad.alloc(sizeof(uint32_t), s));
+  PFS_HIP(ctx, d_table.alloc(sizeof(uint32_t) * nruns, s));
+  PFS_HIP(ctx, d_coffs.alloc(sizeof(uint64_t) * (nchunks + 1), s));
+  PFS_HIP(ctx, d_bad.alloc(sizeof(uint32_t), s));
   if (nruns) {
     uint32_t bad = 0;
-    RES_HIP(ctx, hipMemcpyAsync(d_table.p, b.table.data(), sizeof(uint32_t) * nruns,
+    PFS_HIP(ctx, hipMemcpyAsync(d_table.p, b.table.data(), sizeof(uint32_t) * nruns,
                                 hipMemcpyHostToDevice, s));
-    RES_HIP(ctx, hipMemcpyAsync(d_coffs.p, b.offs.data(), sizeof(uint64_t) * (nchunks + 1),
+    PFS_HIP(ctx, hipMemcpyAsync(d_coffs.p, b.offs.data(), sizeof(uint64_t) * (nchunks + 1),
                                 hipMemcpyHostToDevice, s));
-    RES_HIP(ctx, hipMemsetAsync(d_bad.p, 0, sizeof bad, s));
+    PFS_HIP(ctx, hipMemsetAsync(d_bad.p, 0, sizeof bad, s));
     rs.n[6] += sizeof(uint32_t) * nruns + sizeof(uint64_t) * (nchunks + 1);
-    RES_HIP(ctx, launch_rtar_chunks(d_slices.as<pfscdc_slice>(), m, d_table.as<uint32_t>(),
+    PFS_HIP(ctx, launch_rtar_chunks(d_slices.as<pfscdc_slice>(), m, d_table.as<uint32_t>(),
                                     d_coffs.as<uint64_t>(), nchunks, d_bad.as<uint32_t>(), cus, s));
-    RES_HIP(ctx, hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
-    RES_HIP(ctx, hipStreamSynchronize(s));
+    PFS_HIP(ctx, hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
+    PFS_HIP(ctx, hipStreamSynchronize(s));
     rs.n[5] += sizeof bad;
     if (bad) return ctx_fail(ctx, PFSCDC_ECORRUPT, "a DataRef reaches past its stored chunk");
   }

@@ -1,43 +1,16 @@
 // source_dev.cpp — the Source over a device-resident list (pfscdc_source_open): the driver of
 // the src_* kernels (cdc_kernels.hip §11) and the hand-over to the host arm (source.cpp).
-#include <chrono>
-#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "dev_list.h"
-#include "index_list.h"
-#include "pfscdc_internal.h"
+#include "dev_pass.h"
 #include "source.h"
 
 namespace {
 
 using namespace pfscdc;
 using List = pfscdc_index_list;
-
-#define SRC_HIP(ctx, expr)                                                             \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return pfscdc::ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PFSCDC_ENOMEM : PFSCDC_EHIP, \
-                              std::string(#expr) + ": " + hipGetErrorString(e_));      \
-  } while (0)
-
-struct Clock {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  float lap() {  // ms since the last lap
-    const auto t1 = std::chrono::steady_clock::now();
-    const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-    t0 = t1;
-    return ms;
-  }
-};
-
-RtarList view(const pfscdc_dev_list& d) {
-  return RtarList{(const pfscdc_index_entry*)d.entries, (const char*)d.blob,
-                  (const pfscdc_full_dataref*)d.drs, d.n, d.nr, d.nb};
-}
 
 // NewErrOnEmpty: getFile, and inspect / walk below the root; never a side of diffFile
 // (PFSCDC_SRC_DIFF), whose missing path is an empty side
@@ -48,53 +21,41 @@ bool errs_on_empty(const SrcArg& a) {
 // The host arm: the list comes to the host, pfscdc_source_host's body runs, its result goes back.
 int host_arm(pfscdc_ctx* ctx, const pfscdc_dev_list& in, const SrcArg& a, const uint8_t* leaf,
              int leaf_on_device, pfscdc_source** out) {
-  SourceStats& st = ctx_source_stats(ctx);
+  PassStats& st = ctx_source_stats(ctx);
   Clock clk;
   hipStream_t s = ctx_stream(ctx);
   List l, res;
   if (int rc = dev_list_download(ctx, in, &l)) return rc;
-  st.n[7] += sizeof(pfscdc_index_entry) * in.n + sizeof(pfscdc_full_dataref) * in.nr + in.nb;
+  st.n[7] += list_bytes(in);
   std::vector<uint8_t> hleaf;
   if (leaf && leaf_on_device && in.n) {
     hleaf.resize(32 * in.n);
-    SRC_HIP(ctx, hipMemcpyAsync(hleaf.data(), leaf, hleaf.size(), hipMemcpyDeviceToHost, s));
-    SRC_HIP(ctx, hipStreamSynchronize(s));
+    PFS_HIP(ctx, hipMemcpyAsync(hleaf.data(), leaf, hleaf.size(), hipMemcpyDeviceToHost, s));
+    PFS_HIP(ctx, hipStreamSynchronize(s));
     st.n[7] += hleaf.size();
     leaf = hleaf.data();
   }
   std::vector<pfscdc_file_info> infos;
   std::string err;
   if (int rc = source_host(l, a, leaf, &res, &infos, &err, &st.n[3])) return ctx_fail(ctx, rc, err);
-  std::unique_ptr<pfscdc_source> src(new pfscdc_source());
-  src->device = ctx_device(ctx);
-  if (int rc = dev_list_upload(ctx, res, &src->list)) return rc;
-  st.n[6] += sizeof(pfscdc_index_entry) * res.entries.size() +
-             sizeof(pfscdc_full_dataref) * res.drs.size() + res.blob.size();
-  const uint64_t ib = sizeof(pfscdc_file_info) * infos.size();
-  SRC_HIP(ctx, hipMalloc(&src->infos, ib + kGuard));
-  if (ib) {
-    SRC_HIP(ctx, hipMemcpyAsync(src->infos, infos.data(), ib, hipMemcpyHostToDevice, s));
-    SRC_HIP(ctx, hipStreamSynchronize(s));
-    st.n[6] += ib;
-  }
+  if (int rc = source_upload(ctx, res, infos, out, &st.n[6])) return rc;
   st.n[2] = infos.size();
   st.ms[0] = clk.lap();
-  *out = src.release();
   return PFSCDC_OK;
 }
 
 int source_open(pfscdc_ctx* ctx, const pfscdc_dev_list& in, int kind, const char* arg,
                 const uint8_t* leaf, int leaf_on_device, pfscdc_source** out) {
   *out = nullptr;
-  SourceStats& st = ctx_source_stats(ctx);
-  st = SourceStats();
+  PassStats& st = ctx_source_stats(ctx);
+  st = PassStats();
   st.n[1] = in.n;
   if (in.device != ctx_device(ctx))
     return ctx_fail(ctx, PFSCDC_EINVAL, "a resident list of another device");
   SrcArg a;
   std::string err;
   if (int rc = source_arg(kind, arg, &a, &err)) return ctx_fail(ctx, rc, err);
-  SRC_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+  PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
   if (knob(Knob::Source) == 0) return host_arm(ctx, in, a, leaf, leaf_on_device, out);
   hipStream_t s = ctx_stream(ctx);
   const int cus = ctx_num_cus(ctx);
@@ -103,30 +64,30 @@ int source_open(pfscdc_ctx* ctx, const pfscdc_dev_list& in, int kind, const char
   // ---- insert and select: count, prefix sums
   GuardMem d_arg, d_cnt, d_base, d_flags;
   Guards g;
-  SRC_HIP(ctx, d_arg.alloc(a.name.size() + a.dir.size(), s));
-  SRC_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * l.n, s));
-  SRC_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (l.n + 1), s));
+  PFS_HIP(ctx, d_arg.alloc(a.name.size() + a.dir.size(), s));
+  PFS_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * l.n, s));
+  PFS_HIP(ctx, d_base.alloc(sizeof(uint64_t) * 3 * (l.n + 1), s));
   // SrcBad, the deepest depth, the directories inserted
-  SRC_HIP(ctx, d_flags.alloc(4 * sizeof(uint32_t), s));
+  PFS_HIP(ctx, d_flags.alloc(4 * sizeof(uint32_t), s));
   g.add(d_cnt);
   g.add(d_base);
   g.add(d_flags);
   const std::string both = a.name + a.dir;
   if (!both.empty()) {
-    SRC_HIP(ctx, hipMemcpyAsync(d_arg.p, both.data(), both.size(), hipMemcpyHostToDevice, s));
+    PFS_HIP(ctx, hipMemcpyAsync(d_arg.p, both.data(), both.size(), hipMemcpyHostToDevice, s));
     st.n[6] += both.size();
   }
-  SRC_HIP(ctx, hipMemsetAsync(d_flags.p, 0, 4 * sizeof(uint32_t), s));
+  PFS_HIP(ctx, hipMemsetAsync(d_flags.p, 0, 4 * sizeof(uint32_t), s));
   const SrcPred pr{d_arg.as<char>(), d_arg.as<char>() + a.name.size(), (uint32_t)a.name.size(),
                    (uint32_t)a.dir.size(), a.all, a.exclude_dir, a.child_flag, 0};
-  SRC_HIP(ctx, launch_src_count(l, pr, d_cnt.as<MrgCount>(), d_flags.as<uint32_t>(), cus, s));
-  SRC_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), l.n, d_base.as<uint64_t>(), s));
+  PFS_HIP(ctx, launch_src_count(l, pr, d_cnt.as<MrgCount>(), d_flags.as<uint32_t>(), cus, s));
+  PFS_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), l.n, d_base.as<uint64_t>(), s));
   uint64_t totals[3] = {0, 0, 0};
   uint32_t flags[4] = {0, 0, 0, 0};
-  SRC_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 3 * l.n, sizeof totals,
+  PFS_HIP(ctx, hipMemcpyAsync(totals, d_base.as<uint64_t>() + 3 * l.n, sizeof totals,
                               hipMemcpyDeviceToHost, s));
-  SRC_HIP(ctx, hipMemcpyAsync(flags, d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
-  SRC_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, hipMemcpyAsync(flags, d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   st.n[7] += sizeof totals + sizeof flags;
   if (flags[0] & kSrcMalformed)
     return ctx_fail(ctx, PFSCDC_EINVAL, "an entry's strings or DataRefs lie outside the list's arrays");
@@ -135,40 +96,36 @@ int source_open(pfscdc_ctx* ctx, const pfscdc_dev_list& in, int kind, const char
   if (flags[0]) {  // out of order, an unclean path, a directory twice: emit() taken literally
     return host_arm(ctx, in, a, leaf, leaf_on_device, out);
   }
-  const uint64_t m = totals[0], nr = totals[1], nb = totals[2];
+  const uint64_t m = totals[0], nr = totals[1];
   if (m > 0xffffffffull) return ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "more than 2^32 - 1 entries");
   if (nr > l.nr) return ctx_fail(ctx, PFSCDC_EHIP, "source: the counts exceed the input");
   if (m == 0 && errs_on_empty(a)) return ctx_fail(ctx, PFSCDC_ENOTFOUND, source_not_found(a));
   // ---- fill: entries, strings, DataRefs; per output entry its source, depth, type and size
-  GuardMem o_entries, o_blob, o_drs, d_copy, d_meta, d_infos, d_sizes, d_sbase;
-  SRC_HIP(ctx, o_entries.alloc(sizeof(pfscdc_index_entry) * m, s));
-  SRC_HIP(ctx, o_blob.alloc(nb, s));
-  SRC_HIP(ctx, o_drs.alloc(sizeof(pfscdc_full_dataref) * nr, s));
-  SRC_HIP(ctx, d_copy.alloc(sizeof(MrgCopy) * l.n, s));
-  SRC_HIP(ctx, d_meta.alloc(sizeof(SrcMeta) * m, s));
-  SRC_HIP(ctx, d_infos.alloc(sizeof(pfscdc_file_info) * m, s));
-  SRC_HIP(ctx, d_sizes.alloc(sizeof(MrgCount) * m, s));
-  SRC_HIP(ctx, d_sbase.alloc(sizeof(uint64_t) * 3 * (m + 1), s));
-  for (const GuardMem* x : {&o_entries, &o_blob, &o_drs, &d_copy, &d_meta, &d_infos, &d_sizes, &d_sbase})
-    g.add(*x);
-  if (l.n) SRC_HIP(ctx, hipMemsetAsync(d_copy.p, 0, sizeof(MrgCopy) * l.n, s));
-  SRC_HIP(ctx, launch_src_fill(l, pr, d_cnt.as<MrgCount>(), d_base.as<uint64_t>(),
-                               o_entries.as<pfscdc_index_entry>(), o_blob.as<char>(),
+  OutList o;
+  GuardMem d_copy, d_meta, d_infos, d_sizes, d_sbase;
+  PFS_HIP(ctx, o.alloc(totals, s, &g));
+  PFS_HIP(ctx, copy_plan_alloc(&d_copy, l.n, s, &g));
+  PFS_HIP(ctx, d_meta.alloc(sizeof(SrcMeta) * m, s));
+  PFS_HIP(ctx, d_infos.alloc(sizeof(pfscdc_file_info) * m, s));
+  PFS_HIP(ctx, d_sizes.alloc(sizeof(MrgCount) * m, s));
+  PFS_HIP(ctx, d_sbase.alloc(sizeof(uint64_t) * 3 * (m + 1), s));
+  for (const GuardMem* x : {&d_meta, &d_infos, &d_sizes, &d_sbase}) g.add(*x);
+  PFS_HIP(ctx, launch_src_fill(l, pr, d_cnt.as<MrgCount>(), d_base.as<uint64_t>(),
+                               o.entries.as<pfscdc_index_entry>(), o.blob.as<char>(),
                                d_copy.as<MrgCopy>(), d_meta.as<SrcMeta>(),
                                d_infos.as<pfscdc_file_info>(), d_sizes.as<MrgCount>(),
-                               d_flags.as<uint32_t>() + 1, o_drs.as<pfscdc_full_dataref>(), cus, s));
-  SRC_HIP(ctx, hipStreamSynchronize(s));
+                               d_flags.as<uint32_t>() + 1, o.drs.as<pfscdc_full_dataref>(), cus, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   st.ms[0] = clk.lap();
   // ---- subtree ends and directory sizes
-  const RtarList ol{o_entries.as<pfscdc_index_entry>(), o_blob.as<char>(),
-                    o_drs.as<pfscdc_full_dataref>(), m, nr, nb};
-  SRC_HIP(ctx, launch_merge_scan(d_sizes.as<MrgCount>(), m, d_sbase.as<uint64_t>(), s));
-  SRC_HIP(ctx, launch_src_tree(ol, d_meta.as<SrcMeta>(), d_sbase.as<uint64_t>(),
+  const RtarList ol = o.view();
+  PFS_HIP(ctx, launch_merge_scan(d_sizes.as<MrgCount>(), m, d_sbase.as<uint64_t>(), s));
+  PFS_HIP(ctx, launch_src_tree(ol, d_meta.as<SrcMeta>(), d_sbase.as<uint64_t>(),
                                d_infos.as<pfscdc_file_info>(), cus, s));
   // only the deepest depth comes back, to size the level loop
-  SRC_HIP(ctx, hipMemcpyAsync(flags, d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
-  SRC_HIP(ctx, g.fetch(s));
-  SRC_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, hipMemcpyAsync(flags, d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, g.fetch(s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   st.n[7] += sizeof flags + g.host.size();
   if (!g.ok()) return ctx_fail(ctx, PFSCDC_EHIP, "source: a kernel wrote past its array");
   st.ms[1] = clk.lap();
@@ -179,80 +136,70 @@ int source_open(pfscdc_ctx* ctx, const pfscdc_dev_list& in, int kind, const char
   GuardMem d_buf, d_segs, d_order, d_qctr, d_offs, d_lcnt, d_lbase;
   Guards gh;
   const uint64_t buf_bytes = 32 * (m > nr ? m : nr);
-  SRC_HIP(ctx, d_buf.alloc(buf_bytes, s));
-  SRC_HIP(ctx, d_segs.alloc(sizeof(pfscdc_segment) * m, s));
-  SRC_HIP(ctx, d_order.alloc(sizeof(uint32_t) * m, s));
-  SRC_HIP(ctx, d_qctr.alloc(2 * sizeof(uint32_t), s));
-  SRC_HIP(ctx, d_offs.alloc(2 * sizeof(uint64_t), s));  // one "file": the buffer, from 0
-  SRC_HIP(ctx, d_lcnt.alloc(sizeof(MrgCount) * m, s));
-  SRC_HIP(ctx, d_lbase.alloc(sizeof(uint64_t) * 3 * (m + 1), s));
+  PFS_HIP(ctx, d_buf.alloc(buf_bytes, s));
+  PFS_HIP(ctx, d_segs.alloc(sizeof(pfscdc_segment) * m, s));
+  PFS_HIP(ctx, d_order.alloc(sizeof(uint32_t) * m, s));
+  PFS_HIP(ctx, d_qctr.alloc(2 * sizeof(uint32_t), s));
+  PFS_HIP(ctx, d_offs.alloc(2 * sizeof(uint64_t), s));  // one "file": the buffer, from 0
+  PFS_HIP(ctx, d_lcnt.alloc(sizeof(MrgCount) * m, s));
+  PFS_HIP(ctx, d_lbase.alloc(sizeof(uint64_t) * 3 * (m + 1), s));
   for (const GuardMem* x : {&d_buf, &d_segs, &d_order, &d_qctr, &d_offs, &d_lcnt, &d_lbase, &d_infos})
     gh.add(*x);
   const int64_t forced = knob(Knob::HashWaves);
   const int waves = forced >= 1 && forced <= 8 ? (int)forced : 0;
   if (m) {
     const uint64_t offs[2] = {0, buf_bytes};
-    SRC_HIP(ctx, hipMemcpyAsync(d_offs.p, offs, sizeof offs, hipMemcpyHostToDevice, s));
-    SRC_HIP(ctx, hipMemsetAsync(d_qctr.p, 0, 2 * sizeof(uint32_t), s));
+    PFS_HIP(ctx, hipMemcpyAsync(d_offs.p, offs, sizeof offs, hipMemcpyHostToDevice, s));
+    PFS_HIP(ctx, hipMemsetAsync(d_qctr.p, 0, 2 * sizeof(uint32_t), s));
     st.n[6] += sizeof offs;
     GuardMem d_leaf;
     if (leaf) {  // the caller's: MergeFileReader.Hash per file
       if (!leaf_on_device) {
-        SRC_HIP(ctx, d_leaf.alloc(32 * l.n, s));
-        SRC_HIP(ctx, hipMemcpyAsync(d_leaf.p, leaf, 32 * l.n, hipMemcpyHostToDevice, s));
+        PFS_HIP(ctx, d_leaf.alloc(32 * l.n, s));
+        PFS_HIP(ctx, hipMemcpyAsync(d_leaf.p, leaf, 32 * l.n, hipMemcpyHostToDevice, s));
         st.n[6] += 32 * l.n;
         leaf = d_leaf.as<uint8_t>();
       }
-      SRC_HIP(ctx, launch_src_leaf_copy(d_meta.as<SrcMeta>(), leaf, m, d_infos.as<pfscdc_file_info>(),
+      PFS_HIP(ctx, launch_src_leaf_copy(d_meta.as<SrcMeta>(), leaf, m, d_infos.as<pfscdc_file_info>(),
                                         cus, s));
     } else {  // hashDataRefs: one record per entry (a directory's is empty and overwritten below)
-      SRC_HIP(ctx, launch_src_leaf(ol, d_buf.as<uint8_t>(), d_segs.as<pfscdc_segment>(), cus, s));
+      PFS_HIP(ctx, launch_src_leaf(ol, d_buf.as<uint8_t>(), d_segs.as<pfscdc_segment>(), cus, s));
       // the records' count: the entries emitted, base[3 n] of the first prefix sums
-      SRC_HIP(ctx, launch_blake2b(d_buf.as<uint8_t>(), d_offs.as<uint64_t>(), d_segs.as<pfscdc_segment>(),
+      PFS_HIP(ctx, launch_blake2b(d_buf.as<uint8_t>(), d_offs.as<uint64_t>(), d_segs.as<pfscdc_segment>(),
                                   d_base.as<uint64_t>() + 3 * l.n, m, d_order.as<uint32_t>(),
                                   d_qctr.as<uint32_t>(), cus, buf_bytes, s, false, nullptr, waves));
       st.n[5]++;
-      SRC_HIP(ctx, launch_src_scatter(d_meta.as<SrcMeta>(), nullptr, d_segs.as<pfscdc_segment>(), m,
+      PFS_HIP(ctx, launch_src_scatter(d_meta.as<SrcMeta>(), nullptr, d_segs.as<pfscdc_segment>(), m,
                                       -1, d_infos.as<pfscdc_file_info>(), cus, s));
     }
-    SRC_HIP(ctx, hipStreamSynchronize(s));
+    PFS_HIP(ctx, hipStreamSynchronize(s));
     st.ms[2] = clk.lap();
     // the directories, deepest first (those of the deepest depth are empty)
     for (uint32_t level = maxdepth + 1; level-- > 0;) {
-      SRC_HIP(ctx, launch_src_level_count(d_meta.as<SrcMeta>(), d_infos.as<pfscdc_file_info>(), m,
+      PFS_HIP(ctx, launch_src_level_count(d_meta.as<SrcMeta>(), d_infos.as<pfscdc_file_info>(), m,
                                           level, d_lcnt.as<MrgCount>(), cus, s));
-      SRC_HIP(ctx, launch_merge_scan(d_lcnt.as<MrgCount>(), m, d_lbase.as<uint64_t>(), s));
-      SRC_HIP(ctx, launch_src_level_gather(d_meta.as<SrcMeta>(), d_infos.as<pfscdc_file_info>(),
+      PFS_HIP(ctx, launch_merge_scan(d_lcnt.as<MrgCount>(), m, d_lbase.as<uint64_t>(), s));
+      PFS_HIP(ctx, launch_src_level_gather(d_meta.as<SrcMeta>(), d_infos.as<pfscdc_file_info>(),
                                            d_lbase.as<uint64_t>(), m, level, d_buf.as<uint8_t>(),
                                            d_segs.as<pfscdc_segment>(), cus, s));
-      SRC_HIP(ctx, launch_blake2b(d_buf.as<uint8_t>(), d_offs.as<uint64_t>(), d_segs.as<pfscdc_segment>(),
+      PFS_HIP(ctx, launch_blake2b(d_buf.as<uint8_t>(), d_offs.as<uint64_t>(), d_segs.as<pfscdc_segment>(),
                                   d_lbase.as<uint64_t>() + 3 * m + 1, m, d_order.as<uint32_t>(),
                                   d_qctr.as<uint32_t>(), cus, buf_bytes, s, false, nullptr, waves));
       st.n[5]++;
-      SRC_HIP(ctx, launch_src_scatter(d_meta.as<SrcMeta>(), d_lbase.as<uint64_t>(),
+      PFS_HIP(ctx, launch_src_scatter(d_meta.as<SrcMeta>(), d_lbase.as<uint64_t>(),
                                       d_segs.as<pfscdc_segment>(), m, (int)level,
                                       d_infos.as<pfscdc_file_info>(), cus, s));
     }
     st.n[4] = (uint64_t)maxdepth + 1;
   }
-  SRC_HIP(ctx, gh.fetch(s));
-  SRC_HIP(ctx, hipStreamSynchronize(s));
+  PFS_HIP(ctx, gh.fetch(s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   st.n[7] += gh.host.size();
   if (!gh.ok()) return ctx_fail(ctx, PFSCDC_EHIP, "source: a kernel wrote past its array");
   st.ms[3] = clk.lap();
-  std::unique_ptr<pfscdc_source> src(new pfscdc_source());
-  src->device = ctx_device(ctx);
-  src->list = dev_list_new(ctx);
-  src->list->n = m;
-  src->list->nr = nr;
-  src->list->nb = nb;
-  src->list->entries = o_entries.release();
-  src->list->blob = o_blob.release();
-  src->list->drs = o_drs.release();
-  src->infos = d_infos.release();
   st.n[0] = 1;
   st.n[2] = m;
-  *out = src.release();
+  *out = source_new(ctx, &o, &d_infos);
   return PFSCDC_OK;
 }
 
@@ -276,8 +223,7 @@ int pfscdc_source_open_list(pfscdc_ctx* ctx, const pfscdc_index_list* in, int ki
   pfscdc_dev_list* d = nullptr;
   if (int rc = pfscdc::dev_list_upload(ctx, l, &d)) return rc;
   const int rc = source_open(ctx, *d, kind, arg, leaf_hashes, leaf_on_device, out);
-  pfscdc::ctx_source_stats(ctx).n[6] += sizeof(pfscdc_index_entry) * l.entries.size() +
-                                        sizeof(pfscdc_full_dataref) * l.drs.size() + l.blob.size();
+  pfscdc::ctx_source_stats(ctx).n[6] += pfscdc::list_bytes(l);
   delete d;
   return rc;
 }
@@ -293,10 +239,10 @@ int pfscdc_source_infos(pfscdc_ctx* ctx, const pfscdc_source* s, pfscdc_file_inf
   if (!s->list->n) return PFSCDC_OK;
   if (!out) return PFSCDC_EINVAL;
   hipStream_t st = pfscdc::ctx_stream(ctx);
-  SRC_HIP(ctx, hipSetDevice(s->device));
-  SRC_HIP(ctx, hipMemcpyAsync(out, s->infos, sizeof(pfscdc_file_info) * s->list->n,
+  PFS_HIP(ctx, hipSetDevice(s->device));
+  PFS_HIP(ctx, hipMemcpyAsync(out, s->infos, sizeof(pfscdc_file_info) * s->list->n,
                               hipMemcpyDeviceToHost, st));
-  SRC_HIP(ctx, hipStreamSynchronize(st));
+  PFS_HIP(ctx, hipStreamSynchronize(st));
   return PFSCDC_OK;
 }
 
@@ -308,15 +254,11 @@ int pfscdc_source_free(pfscdc_source* s) {
 }
 
 int pfscdc_last_source_stats(pfscdc_ctx* ctx, uint64_t out[8]) {
-  if (!ctx || !out) return PFSCDC_EINVAL;
-  std::memcpy(out, pfscdc::ctx_source_stats(ctx).n, sizeof(uint64_t) * 8);
-  return PFSCDC_OK;
+  return pfscdc::last_pass_stats(ctx, pfscdc::ctx_source_stats, out, nullptr);
 }
 
 int pfscdc_last_source_timings(pfscdc_ctx* ctx, float out[4]) {
-  if (!ctx || !out) return PFSCDC_EINVAL;
-  std::memcpy(out, pfscdc::ctx_source_stats(ctx).ms, sizeof(float) * 4);
-  return PFSCDC_OK;
+  return pfscdc::last_pass_stats(ctx, pfscdc::ctx_source_stats, nullptr, out);
 }
 
 }  // extern "C"
