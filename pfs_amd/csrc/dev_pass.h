@@ -1,5 +1,5 @@
 // dev_pass.h — what the drivers of the index list passes share (index.cpp, resident.cpp,
-// source_dev.cpp, diff_dev.cpp, copy_map_dev.cpp): the HIP error macro, the lap clock, the views
+// source_dev.cpp, diff_dev.cpp, copy_map_dev.cpp): the lap clock, the views
 // and byte sizes of a list, the scratch and the guarded device arrays, the output list of a pass,
 // the upload of a host-made Source and the body of the pfscdc_last_*_stats calls.  It needs HIP:
 // the host arms (source.cpp, diff.cpp, copy_map.cpp, index_decode.cpp, index_merge.cpp) stay
@@ -13,15 +13,6 @@
 #include "dev_list.h"
 #include "index_list.h"
 #include "pfscdc_internal.h"
-
-// a failed HIP call fails the ctx's call: PFSCDC_ENOMEM or PFSCDC_EHIP, the expression in the text
-#define PFS_HIP(ctx, expr)                                                             \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return pfscdc::ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PFSCDC_ENOMEM : PFSCDC_EHIP, \
-                              std::string(#expr) + ": " + hipGetErrorString(e_));      \
-  } while (0)
 
 namespace pfscdc {
 

@@ -259,6 +259,14 @@ hipError_t launch_tar_frame(const TarEntry* d_entries, const uint8_t* d_names, u
                             uint64_t begin, uint64_t end, uint64_t total, uint8_t* out,
                             int num_cus, hipStream_t st);
 int ctx_fail(pfscdc_ctx* ctx, int code, const std::string& msg);  // sets pfscdc_last_error
+// a failed HIP call fails the ctx's call: PFSCDC_ENOMEM or PFSCDC_EHIP, the expression in the text
+#define PFS_HIP(ctx, expr)                                                             \
+  do {                                                                                 \
+    hipError_t e_ = (expr);                                                            \
+    if (e_ != hipSuccess)                                                              \
+      return pfscdc::ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PFSCDC_ENOMEM : PFSCDC_EHIP, \
+                              std::string(#expr) + ": " + hipGetErrorString(e_));      \
+  } while (0)
 // pfscdc_read_slices; strict: PFSCDC_ECORRUPT, before anything is written to out, if a chunk
 // that a slice names fails verification (pfscdc_store_read).  tar (nullable; pfscdc_read_tar):
 // slices are tar->pieces in order, slice i goes to out + tar->pieces[i].out_off instead of
