@@ -355,6 +355,12 @@ PFS_DEV uint64_t readlane_u64(uint64_t v, uint32_t lane) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+PFS_DEV uint64_t readfirstlane_u64(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+
 // Cut skipping (ScanPlan), at the start of a unit: the unit behind dispatch slot `slot`
 // belongs to file f, `rank` units past the unit holding the file's first eligible position
 // E = fs + min - 1.  One returning agent-scope atomic per lane reads the file's 64 rank slots
@@ -479,7 +485,16 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(kSca
     uint64_t unit = slot;
     uint32_t skip = 0;
     uint32_t fr = ~0u;  // the file this unit reports to | its rank << 24 (~0u: none)
-    if (plan) scan_unit_plan(plan, slot, lane, n, unit, skip, fr);
+    if (plan) {
+      scan_unit_plan(plan, slot, lane, n, unit, skip, fr);
+      // every lane holds the same unit, skip and fr (the slot is wave-uniform and the replay
+      // runs on ballots and readlane), but they come out of vector loads: read them back as
+      // scalars, so that the unit's addresses, its step count and its buffer descriptor live
+      // in SGPRs (EXEC is full here: the unit loop is wave-level)
+      unit = readfirstlane_u64(unit);
+      skip = (uint32_t)__builtin_amdgcn_readfirstlane((int)skip);
+      fr = (uint32_t)__builtin_amdgcn_readfirstlane((int)fr);
+    }
     const uint64_t tile = unit / kScanWaves;
     const uint64_t wslot = unit % kScanWaves;
     TileRec* const rec = recs + tile;
