@@ -316,6 +316,20 @@ int pfscdc_hash_ranges(pfscdc_ctx* ctx, const void* bytes, uint64_t nbytes, int 
  * candidate-scan kernel. */
 uint64_t pfscdc_debug_candidates(pfscdc_ctx* ctx, uint64_t* out, uint64_t cap);
 
+/* Two more test hooks, valid after a completed scan (pfscdc_wait) and before the next call
+ * that stages records on the ctx; neither is part of the product path.
+ *
+ * The hash queue the last scan built: order[0, qlen) are segment indices in dispatch order;
+ * next[0, nseg) are the hash bins' links (0xffffffff: none).  *bin_bytes = the bin size
+ * that scan used (0: no bins, next is then left alone).  At most order_cap / next_cap words
+ * are written.  Returns qlen. */
+uint64_t pfscdc_debug_hash_queue(pfscdc_ctx* ctx, uint32_t* order, uint64_t order_cap,
+                                 uint32_t* next, uint64_t next_cap, uint64_t* bin_bytes);
+/* The cut-skipping plan's dispatch slots, 3 words each: unit, file, skip | rank << 8 (skip in
+ * 8 KiB steps of the 256 KiB unit, rank clamped at 255), in dispatch order; at most cap slots
+ * are written.  Returns their number (0: the scan ran without a plan). */
+uint64_t pfscdc_debug_scan_plan(pfscdc_ctx* ctx, uint32_t* slots, uint64_t cap);
+
 /* Bytes the last pfscdc_scan's candidate kernel actually rolled.  Writer.roll never cuts in
  * the first min - 1 bytes after an Annotate (writer.go:125-128,167-170), so the scan skips
  * that part of every file (in 8 KiB steps of its work units) and the count is below nbytes

@@ -38,7 +38,8 @@ EXPORTED = [
     "pfscdc_stream_handle",
     "pfscdc_scan",
     "pfscdc_scan_async", "pfscdc_wait", "pfscdc_num_segments", "pfscdc_segments",
-    "pfscdc_file_segment_begin", "pfscdc_debug_candidates", "pfscdc_last_timings",
+    "pfscdc_file_segment_begin", "pfscdc_debug_candidates", "pfscdc_debug_hash_queue",
+    "pfscdc_debug_scan_plan", "pfscdc_last_timings",
     "pfscdc_last_scan_bytes", "pfscdc_commit_refs",
     "pfscdc_set_options", "pfscdc_refs", "pfscdc_last_ref_ms", "pfscdc_get_chunks",
     "pfscdc_last_get_ms",
@@ -278,6 +279,8 @@ def load() -> C.CDLL:
             "pfscdc_segments": (P(Segment), [vp]),
             "pfscdc_file_segment_begin": (P(u64), [vp]),
             "pfscdc_debug_candidates": (u64, [vp, P(u64), u64]),
+            "pfscdc_debug_hash_queue": (u64, [vp, vp, u64, vp, u64, P(u64)]),
+            "pfscdc_debug_scan_plan": (u64, [vp, vp, u64]),
             "pfscdc_last_timings": (i32, [vp, P(C.c_float)]),
             "pfscdc_last_scan_bytes": (i32, [vp, P(u64)]),
             "pfscdc_last_scan_mode": (i32, [vp, P(u32)]),

@@ -520,6 +520,29 @@ class Chunker:
         n = self.lib.pfscdc_debug_candidates(self.ctx, out, cap)
         return np.array(out[:min(n, cap)], dtype=np.uint64)
 
+    def debug_hash_queue(self):
+        """The hash queue the last scan built (pfscdc_debug_hash_queue, a test hook):
+        (order uint32[qlen], next uint32[nseg] or None without bins, bin_bytes)."""
+        nseg = int(self.lib.pfscdc_num_segments(self.ctx))
+        order = np.zeros(max(nseg, 1), dtype=np.uint32)
+        nxt = np.zeros(max(nseg, 1), dtype=np.uint32)
+        bb = C.c_uint64(0)
+        qlen = int(self.lib.pfscdc_debug_hash_queue(self.ctx, order.ctypes.data, nseg,
+                                                    nxt.ctypes.data, nseg, C.byref(bb)))
+        if qlen > nseg:
+            raise _lib.PfsCdcError(_lib.PFSCDC_ESTATE,
+                                   f"hash queue of {qlen} entries over {nseg} segments")
+        return order[:qlen], (nxt[:nseg] if bb.value else None), int(bb.value)
+
+    def debug_scan_plan(self) -> np.ndarray:
+        """The cut-skipping plan's dispatch slots of the last scan (pfscdc_debug_scan_plan, a
+        test hook): uint32[nslots, 3] of (unit, file, skip | rank << 8); empty without a plan."""
+        n = int(self.lib.pfscdc_debug_scan_plan(self.ctx, None, 0))
+        slots = np.zeros((max(n, 1), 3), dtype=np.uint32)
+        if n:
+            n = min(n, int(self.lib.pfscdc_debug_scan_plan(self.ctx, slots.ctypes.data, n)))
+        return slots[:n]
+
     def fill_synthetic_pieces(self, tensor, piece_offsets: Sequence[int], file_ids, file_starts,
                               seed: int, mode: int = SYNTH_RANDOM) -> None:
         """Fill a torch uint8 CUDA tensor with pieces of synthetic files: piece i = bytes

@@ -13,12 +13,14 @@
 //                          bank-conflict free; per 3 MiB tile (12 waves) <= 15 candidates
 //                          appended to a global tile record, or a DENSE count.  Reads 1
 //                          byte per file byte; VALU-issue bound in practice.
-//   2. compact_kernel      one workgroup: prefix sum over tiles, each tile's offsets sorted
-//                          by rank -> sorted candidate list.
+//   2. compact_tiles       the scan's last workgroup: prefix sum over tiles, each tile's
+//                          offsets sorted by rank -> sorted candidate list.
 //   3. select_kernel       one wave per file: serial cut selection over the sparse list
 //                          (writer.go:168,179 min/max rule), dense tiles re-rolled in-wave.
-//   4. segcompact_kernel   one workgroup: per-file segment counts -> dense segment list.
-//   5. hash_order_kernel   one workgroup: segments sorted longest-first (LPT queue order).
+//   4. segcompact_block    the selection's last workgroup: per-file segment counts -> dense
+//                          segment list.
+//   5. lpt_order_block     the same workgroup (hash_order_kernel for record batches staged
+//                          elsewhere): segments sorted longest-first (LPT queue order).
 //      blake2b_kernel      resident waves, 4 lanes (a quad) per segment, one BLAKE2b column
 //                          each (DPP quad rotations for the diagonal step), message words
 //                          through double-buffered LDS; quads pull the next segment from
@@ -834,13 +836,6 @@ PFS_DEV void compact_tiles(const TileRec* __restrict__ recs, uint64_t ntiles, ui
   if (threadIdx.x == 0) *n_entries = carry;
 }
 
-__global__ __launch_bounds__(kCompactBlock) void compact_kernel(
-    const TileRec* __restrict__ recs, uint64_t ntiles, uint64_t n,
-    uint64_t* __restrict__ entries, uint64_t* __restrict__ n_entries) {
-  __shared__ uint64_t s_wave[kCompactBlock / 64 + 1];
-  compact_tiles<kCompactBlock>(recs, ntiles, n, entries, n_entries, s_wave);
-}
-
 // Per-file segment counts -> dense segment list in (file, offset) order; returns the total.
 template <int BLOCK>
 PFS_DEV uint64_t segcompact_block(const pfscdc_segment* __restrict__ slots,
@@ -1080,14 +1075,6 @@ __global__ __launch_bounds__(kSelectBlock) void select_kernel(
 // 4. segment compaction (per-file counts -> dense list in (file, offset) order) and the LPT
 //    order of the hash queue
 // ------------------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(kCompactBlock) void segcompact_kernel(
-    const pfscdc_segment* __restrict__ slots, const uint64_t* __restrict__ seg_base,
-    const uint64_t* __restrict__ nseg, uint32_t nfiles, pfscdc_segment* __restrict__ segs,
-    uint64_t* __restrict__ seg_begin) {
-  __shared__ uint64_t s_wave[kCompactBlock / 64 + 1];
-  segcompact_block<kCompactBlock>(slots, seg_base, nseg, nfiles, segs, seg_begin, s_wave);
-}
 
 __global__ __launch_bounds__(kCompactBlock) void hash_order_kernel(
     const pfscdc_segment* __restrict__ segs, const uint64_t* __restrict__ seg_count,
@@ -2355,12 +2342,6 @@ hipError_t launch_scan(const uint8_t* data, const uint8_t* tail, uint64_t n, con
   return hipGetLastError();
 }
 
-hipError_t launch_compact(const TileRec* recs, uint64_t ntiles, uint64_t n, uint64_t* entries,
-                          uint64_t* n_entries, hipStream_t st) {
-  compact_kernel<<<1, kCompactBlock, 0, st>>>(recs, ntiles, n, entries, n_entries);
-  return hipGetLastError();
-}
-
 hipError_t launch_select(const uint8_t* data, const uint64_t* d_table, const uint64_t* entries,
                          const uint64_t* n_entries, const uint64_t* offs,
                          const uint64_t* seg_base, uint32_t nfiles, uint32_t average_bits,
@@ -2376,13 +2357,6 @@ hipError_t launch_select(const uint8_t* data, const uint64_t* d_table, const uin
                                                          min_chunk, max_chunk, slots, nseg,
                                                          done_ctr, segs, seg_begin, order,
                                                          counter, bin_bytes, next, qlen);
-  return hipGetLastError();
-}
-
-hipError_t launch_segcompact(const pfscdc_segment* slots, const uint64_t* seg_base,
-                             const uint64_t* nseg, uint32_t nfiles, pfscdc_segment* segs,
-                             uint64_t* seg_begin, hipStream_t st) {
-  segcompact_kernel<<<1, kCompactBlock, 0, st>>>(slots, seg_base, nseg, nfiles, segs, seg_begin);
   return hipGetLastError();
 }
 

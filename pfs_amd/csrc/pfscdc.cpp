@@ -103,6 +103,7 @@ struct pfscdc_ctx {
   DevBuf<pfscdc_segment> d_slots, d_segs;
   DevBuf<uint32_t> d_order, d_qctr;  // LPT segment order + hash queue counter
   DevBuf<uint32_t> d_next;            // hash bins: each segment's successor in its bin
+  uint64_t bin_bytes = 0;             // the last scan's bin size (0: no bins)
   DevBuf<pfscdc_ref> d_refs;
   DevBuf<uint8_t> d_out;  // get_chunks: plaintext when the caller's output is on the host
   // kernel execution spans: [0,1] scan begin/end, [2,3] hash begin/end; shader-clock sums
@@ -612,6 +613,7 @@ int scan_async_impl(pfscdc_ctx* c, const void* bytes, uint64_t nbytes, int bytes
   const int64_t kb = knob(Knob::HashBinBytes);
   const uint64_t bin_bytes = kb >= 0 ? (uint64_t)kb : (nbytes + quads - 1) / quads;
   c->h_seg_base.p[nfiles] = cap;
+  c->bin_bytes = bin_bytes;
   c->slot_cap = cap;
   c->nfiles = nfiles;
   c->nbytes = nbytes;
@@ -878,6 +880,45 @@ uint64_t pfscdc_debug_candidates(pfscdc_ctx* c, uint64_t* out, uint64_t cap) {
       return 0;
   }
   return ne;
+}
+
+uint64_t pfscdc_debug_hash_queue(pfscdc_ctx* c, uint32_t* order, uint64_t order_cap,
+                                 uint32_t* next, uint64_t next_cap, uint64_t* bin_bytes) {
+  if (bin_bytes) *bin_bytes = 0;
+  if (!c || c->pending || !c->scan_valid || !c->nfiles) return 0;
+  if (bin_bytes) *bin_bytes = c->bin_bytes;
+  if (hipSetDevice(c->device) != hipSuccess) return 0;
+  uint64_t qlen = 0;
+  if (hipMemcpy(&qlen, c->d_counts.p + 4, sizeof qlen, hipMemcpyDeviceToHost) != hipSuccess)
+    return 0;
+  const uint64_t k = std::min(std::min(qlen, order_cap), c->slot_cap);
+  if (order && k &&
+      hipMemcpy(order, c->d_order.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    return 0;
+  const uint64_t m = c->bin_bytes ? std::min(c->nsegs, next_cap) : 0;
+  if (next && m &&
+      hipMemcpy(next, c->d_next.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    return 0;
+  return qlen;
+}
+
+uint64_t pfscdc_debug_scan_plan(pfscdc_ctx* c, uint32_t* slots, uint64_t cap) {
+  if (!c || c->pending || !c->ntiles || !(c->scan_mode & PFSCDC_SCAN_SKIPPED_CUTS)) return 0;
+  if (hipSetDevice(c->device) != hipSuccess) return 0;
+  uint32_t ns = 0;
+  if (hipMemcpy(&ns, c->d_plan.p, sizeof ns, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  const uint64_t k = std::min<uint64_t>(std::min<uint64_t>(ns, cap), c->ntiles * kScanWaves);
+  if (slots && k) {
+    std::vector<uint4> h(k);
+    if (hipMemcpy(h.data(), c->d_uslots.p, k * sizeof(uint4), hipMemcpyDeviceToHost) != hipSuccess)
+      return 0;
+    for (uint64_t i = 0; i < k; i++) {
+      slots[3 * i] = h[i].x;
+      slots[3 * i + 1] = h[i].y;
+      slots[3 * i + 2] = h[i].z;
+    }
+  }
+  return ns;
 }
 
 int pfscdc_last_scan_bytes(pfscdc_ctx* c, uint64_t* out) {

@@ -156,8 +156,6 @@ hipError_t launch_scan_plan(const uint64_t* offs, uint32_t nfiles, uint64_t n, u
                             uint64_t ntiles, uint32_t* skip, uint64_t* scanned, uint32_t* uinfo,
                             uint4* slots, uint32_t* plan, const ScanPlan& hdr, ScanPlan* d_hdr,
                             hipStream_t st);
-hipError_t launch_compact(const TileRec* recs, uint64_t ntiles, uint64_t n, uint64_t* entries,
-                          uint64_t* n_entries, hipStream_t st);
 hipError_t launch_select(const uint8_t* data, const uint64_t* d_table, const uint64_t* entries,
                          const uint64_t* n_entries, const uint64_t* offs,
                          const uint64_t* seg_base, uint32_t nfiles, uint32_t average_bits,
@@ -166,9 +164,6 @@ hipError_t launch_select(const uint8_t* data, const uint64_t* d_table, const uin
                          uint64_t* seg_begin, uint32_t* order, uint32_t* counter,
                          hipStream_t st, uint64_t bin_bytes = 0, uint32_t* next = nullptr,
                          uint64_t* qlen = nullptr);
-hipError_t launch_segcompact(const pfscdc_segment* slots, const uint64_t* seg_base,
-                             const uint64_t* nseg, uint32_t nfiles, pfscdc_segment* segs,
-                             uint64_t* seg_begin, hipStream_t st);
 // Hash issue priority (launcher argument prio): 0 = the default (kHashPrioAuto: raise it for
 // chains of more than 8192 blocks when quads refill), kHashPrioNone = never, else a threshold
 // in 128-B blocks.

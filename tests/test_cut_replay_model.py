@@ -16,6 +16,8 @@ of timings run in seconds.  Test infrastructure only: nothing here runs on the p
 import numpy as np
 import pytest
 
+import scan_models
+
 U = 1024          # work unit (the kernel's kScanUnit, scaled down)
 STEP = U // 32    # skip granularity (kUnitStep)
 SLOTS = 64        # rank slots per file (kRankSlots)
@@ -43,31 +45,9 @@ def select_cuts(cands, fs, fe, mn, mx):
 
 
 def plan_units(offs, mn):
-    """scan_skip_kernel: per unit its static skip (steps), tracked file and rank."""
-    n = int(offs[-1])
-    nfiles = len(offs) - 1
-    kall = U // STEP
-    units = []
-    for u in range((n + U - 1) // U):
-        ub, ue = u * U, min((u + 1) * U, n)
-        f = int(np.searchsorted(offs, ub, side="right") - 1)
-        s, tf, rank = 0, None, 0  # the kernel starts from "scan whole" (a crowded unit)
-        for g in range(f, f + 64):
-            if g >= nfiles or offs[g] >= ue:
-                s = kall
-                break
-            ls, fe = int(offs[g]) + mn - 1, int(offs[g + 1])
-            if ls < fe:
-                first = max(ls, ub)
-                s = (first - ub) // STEP if first < ue else kall
-                tf, rank = g, ub // U - ls // U
-                break
-        if tf is None:
-            s = kall  # plan mode: a crowded unit holds no eligible position, takes no slot
-        if s < kall and ub + s * STEP < ue:
-            units.append((u, tf, rank, s))
-    units.sort(key=lambda t: (min(t[2], 63), t[0]))
-    return units
+    """scan_skip_kernel: per unit its static skip (steps), tracked file and rank (the model
+    the GPU tests hold against the kernel, scan_models.plan_units, at this scaled geometry)."""
+    return scan_models.plan_units(offs, mn, unit=U, step=STEP)
 
 
 def replay(view, f, rank, offs, mn, mx):
