@@ -931,8 +931,18 @@ int pfscdc_last_resident_stats(pfscdc_ctx* ctx, uint64_t out[8]);
  *                       of *?[]{}!()@+^ or a backslash: PFSCDC_EUNSUPPORTED with the glob named;
  *   PFSCDC_SRC_DIFF     diffFile: SUBTREE's predicate and cleaning, but neither side of a diff is
  *                       wrapped in NewErrOnEmpty (driver_file.go:356-383): nothing selected is
- *                       PFSCDC_OK with no entries.
- * PFSCDC_ENOTFOUND (NewErrOnEmpty): nothing selected by GET, or by SUBTREE with p != "".
+ *                       PFSCDC_OK with no entries;
+ *   PFSCDC_SRC_GLOB     getFile / globFile of a glob pattern (the dialect: pfscdc_glob_match below):
+ *                       mf(path) = (path == "/" && glob == "/") || Match(glob, TrimRight(path, "/"))
+ *                       under the `full` filter, so an entry is selected if mf holds for it or it
+ *                       lies under the last directory that matched.  PFSCDC_INFO_MATCH is set in the
+ *                       flags of the entries for which mf holds itself: the whole result is what
+ *                       getFile serves, the entries with the flag are what globFile reports (a
+ *                       matched directory's size and hash cover its whole subtree).  A glob that
+ *                       does not compile: PFSCDC_EINVAL with the glob and the byte offset named;
+ *                       extglob: PFSCDC_EUNSUPPORTED with the glob named.
+ * PFSCDC_ENOTFOUND (NewErrOnEmpty): nothing selected by GET or GLOB, or by SUBTREE with p != ""
+ * (globFile does not wrap its stream: its caller takes this answer of GLOB as an empty result).
  * PFSCDC_EINVAL: an entry with a Range (not a level-0 list), or strings / DataRefs outside the
  * list's arrays. */
 #define PFSCDC_SRC_ALL 0
@@ -940,9 +950,11 @@ int pfscdc_last_resident_stats(pfscdc_ctx* ctx, uint64_t out[8]);
 #define PFSCDC_SRC_LIST 2
 #define PFSCDC_SRC_GET 3
 #define PFSCDC_SRC_DIFF 4
+#define PFSCDC_SRC_GLOB 5
 #define PFSCDC_FILE_TYPE_FILE 1u /* pfs.FileType_FILE */
 #define PFSCDC_FILE_TYPE_DIR 2u  /* pfs.FileType_DIR: the path ends in '/' */
 #define PFSCDC_INFO_CHILD 1u
+#define PFSCDC_INFO_MATCH 2u
 typedef struct pfscdc_file_info {
   uint8_t hash[32];
   int64_t size;
@@ -963,6 +975,27 @@ int pfscdc_source_host(const pfscdc_index_list* in, int kind, const char* arg,
 const char* pfscdc_source_host_error(void);
 void pfscdc_file_infos_free(pfscdc_file_info* infos);
 
+/* The glob dialect of PFSCDC_SRC_GLOB (gobwas/glob syntax with separator '/'; the glob library of
+ * the reference is not in its tree, so DESIGN.md writes the dialect down): * any run of non-'/'
+ * bytes, ** any run of bytes, ? one non-'/' byte, [...] and [!...] a class of bytes and lo-hi
+ * ranges (it may hold '/'), {a,b} alternatives that nest, \c the byte c; bytewise, the whole
+ * string.  *matched = mf(path) for glob = cleanPath(glob): the backtracking matcher that is the
+ * specification of what the device computes, with no GPU call.  PFSCDC_EINVAL (a stray ] or }, an
+ * unterminated [ or {, an empty class, a range with hi < lo, a trailing backslash) and
+ * PFSCDC_EUNSUPPORTED (extglob: an unescaped ! ( ) @ + ^ outside a class) with
+ * pfscdc_source_host_error naming the glob and the byte offset. */
+int pfscdc_glob_match(const char* glob, const char* path, int* matched);
+/* globLiteralPrefix(cleanPath(glob)): the glob up to its first of * ? [ ] { } ! ( ) @ + ^, as a
+ * C string in out[0, cap) (PFSCDC_EINVAL if it does not fit). */
+int pfscdc_glob_literal_prefix(const char* glob, char* out, size_t cap);
+/* Test hook: the position automaton compiled from cleanPath(glob), what the device stages.
+ * out[0, 64) follow, out[64, 320) accept_byte (masks of positions), out[320] first, out[321] last,
+ * out[322] nullable, out[323] the positions (more than 64: no program, the masks are zero).  A
+ * string is accepted iff, with T = first and acc = nullable before its first byte and per byte c
+ * S = T & accept_byte[c], acc = (S & last) != 0, T = OR of follow[b] over the bits b of S, acc
+ * holds after its last byte. */
+int pfscdc_debug_glob_program(const char* glob, uint64_t out[324]);
+
 /* The Source over a resident list on ctx.  The PFSCDC_SOURCE knob: 1 runs the device arm
  * (per input entry the new ancestors by the common prefix with its predecessor and the predicate on
  * each, prefix sums, a fill at the item's own ranges and the DataRef copy; per output entry its depth
@@ -971,7 +1004,11 @@ void pfscdc_file_infos_free(pfscdc_file_info* infos);
  * hashes gathered 32 bytes apart), 0 downloads the list, calls pfscdc_source_host and uploads its
  * result; list and infos are identical.  The device arm hands a call to the host arm for a list
  * that is not in (path, tag) order, that holds a path not IsClean(p, IsDir(p)), or that holds one
- * directory path twice; pfscdc_last_source_stats says which ran.  leaf_hashes as
+ * directory path twice; pfscdc_last_source_stats says which ran.  PFSCDC_SRC_GLOB on the device:
+ * one kernel ahead of the count pass walks each path once through the glob's position automaton
+ * (pfscdc_debug_glob_program) and leaves one 64-bit mask per entry, which the count and fill
+ * passes read in place of a predicate; a glob of more than 64 positions or a path of more than
+ * 63 '/' hands the call to the host arm.  leaf_hashes as
  * pfscdc_source_host's, on the device when leaf_on_device.  Errors and their texts
  * (pfscdc_last_error) as pfscdc_source_host's, with *out NULL.  Every array the kernels fill ends
  * in a 64-byte guard that the call checks (PFSCDC_EHIP). */
@@ -998,6 +1035,14 @@ int pfscdc_last_source_stats(pfscdc_ctx* ctx, uint64_t out[8]);
  * sums, fill, DataRef copy; host arm: the download, the host call and the upload), out[1] depths,
  * subtree ends and sizes, out[2] the leaf hashes, out[3] the directory levels. */
 int pfscdc_last_source_timings(pfscdc_ctx* ctx, float out[4]);
+/* Test hook: the glob kernel alone over a resident list, so that it is held against
+ * pfscdc_glob_match directly.  masks[i] of entry i's path: bit j = the bytes before its j-th '/'
+ * (j from 0: the root, the empty string) are matched by cleanPath(glob), a directory's own final
+ * '/' included; bit 63 = a path that does not end in '/' is matched as a whole.  *bad: 32 if a
+ * path holds more than 63 '/' (its mask is then not used), else 0.  PFSCDC_EUNSUPPORTED for a
+ * glob of more than 64 positions; compile errors as pfscdc_glob_match's (pfscdc_last_error). */
+int pfscdc_debug_glob_masks(pfscdc_ctx* ctx, const pfscdc_dev_list* list, const char* glob,
+                            uint64_t* masks, uint32_t* bad);
 
 /* ---- DiffFile: two Sources joined by path (src/server/pfs/server/diff.go:22-96) -----------------
  * Differ.Iterate walks sides a (the old commit; emptySource when there is none) and b (the new

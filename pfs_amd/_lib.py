@@ -83,6 +83,8 @@ EXPORTED = [
     "pfscdc_source_open", "pfscdc_source_open_list", "pfscdc_source_list", "pfscdc_source_count",
     "pfscdc_source_infos", "pfscdc_source_free", "pfscdc_last_source_stats",
     "pfscdc_last_source_timings",
+    "pfscdc_glob_match", "pfscdc_glob_literal_prefix", "pfscdc_debug_glob_program",
+    "pfscdc_debug_glob_masks",
     "pfscdc_diff_host", "pfscdc_diff_pairs_free", "pfscdc_source_diff", "pfscdc_diff_count",
     "pfscdc_diff_pairs", "pfscdc_diff_side", "pfscdc_diff_free", "pfscdc_last_diff_stats",
     "pfscdc_last_diff_timings",
@@ -157,9 +159,9 @@ class FileInfoC(C.Structure):
                 ("flags", C.c_uint32)]
 
 
-SRC_ALL, SRC_SUBTREE, SRC_LIST, SRC_GET, SRC_DIFF = 0, 1, 2, 3, 4
+SRC_ALL, SRC_SUBTREE, SRC_LIST, SRC_GET, SRC_DIFF, SRC_GLOB = 0, 1, 2, 3, 4, 5
 FILE_TYPE_FILE, FILE_TYPE_DIR = 1, 2
-INFO_CHILD = 1
+INFO_CHILD, INFO_MATCH = 1, 2
 DIFF_NONE = 0xFFFFFFFF
 
 
@@ -414,6 +416,10 @@ def load() -> C.CDLL:
             "pfscdc_source_free": (i32, [vp]),
             "pfscdc_last_source_stats": (i32, [vp, P(u64)]),
             "pfscdc_last_source_timings": (i32, [vp, P(C.c_float)]),
+            "pfscdc_glob_match": (i32, [C.c_char_p, C.c_char_p, P(i32)]),
+            "pfscdc_glob_literal_prefix": (i32, [C.c_char_p, C.c_char_p, C.c_size_t]),
+            "pfscdc_debug_glob_program": (i32, [C.c_char_p, P(u64)]),
+            "pfscdc_debug_glob_masks": (i32, [vp, vp, C.c_char_p, P(u64), P(u32)]),
             "pfscdc_diff_host": (i32, [vp, P(FileInfoC), vp, P(FileInfoC), P(P(DiffPairC)),
                                        P(u64)]),
             "pfscdc_diff_pairs_free": (None, [P(DiffPairC)]),

@@ -3467,6 +3467,85 @@ PFS_DEV bool src_follows(const RtarList& in, uint64_t i, const pfscdc_index_entr
   return true;
 }
 
+// 11g glob   (PFSCDC_SRC_GLOB, ahead of 11a) one lane per input entry walks its path once through
+//     the glob's position automaton (glob.cpp: at most 64 positions, the set of live ones one
+//     uint64_t): per byte c, S = T & accept_byte[c], T = OR of follow[b] over the bits b of S.
+//     At the j-th '/' it records in bit j of the entry's mask whether the bytes before it are
+//     accepted, which is mf of the directory p[0..k] (TrimRight drops that one '/' of a clean
+//     path), and in bit 63 whether a path that is no directory is accepted whole.  For clean
+//     paths in ascending order the `full` filter selects an entry iff mf holds for it or for one
+//     of its directory prefixes (tests/test_glob_cpu.py holds that against the literal filter),
+//     so the count and fill passes read: the directory ending at '/' j is selected iff a bit
+//     <= j is set, the entry iff any bit is, and PFSCDC_INFO_MATCH is the own bit.
+//     The program is staged into LDS once per workgroup.  follow[] is indexed by the bits of S
+//     and accept_byte[] by the path byte, both per lane, so neither can sit in SGPRs.  A 64-bit
+//     LDS read has 64 banks of 4 bytes per 32-lane half, so entries 32 apart share a bank pair:
+//     'A'..'Z' against 'a'..'z', and each against the digits and punctuation 32 below.  Entry c
+//     is therefore staged at c ^ (c >> 5), which moves the eight blocks of 32 apart by one entry
+//     each; lanes on the same byte (a common prefix) read one address and broadcast.
+constexpr int kGlobFollow = 64, kGlobWords = 64 + 256;
+
+PFS_DEV uint32_t glob_accept_slot(uint32_t c) { return kGlobFollow + (c ^ (c >> 5)); }
+
+__global__ __launch_bounds__(kIdxBlock) void src_glob_kernel(RtarList in,
+                                                             const uint64_t* __restrict__ prog,
+                                                             uint64_t first, uint64_t last,
+                                                             uint32_t nullable,
+                                                             uint64_t* __restrict__ masks,
+                                                             uint32_t* __restrict__ bad) {
+  __shared__ uint64_t lds[kGlobWords];
+  for (uint32_t w = threadIdx.x; w < kGlobWords; w += kIdxBlock)
+    lds[w < kGlobFollow ? w : glob_accept_slot(w - kGlobFollow)] = prog[w];
+  __syncthreads();
+  for (uint64_t i = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; i < in.n;
+       i += (uint64_t)gridDim.x * kIdxBlock) {
+    const pfscdc_index_entry e = in.entries[i];
+    uint64_t mask = 0;
+    if (src_entry_ok(in, e)) {  // (else the count pass answers kSrcMalformed)
+      const uint8_t* s = (const uint8_t*)in.blob + e.path_off;
+      const uint32_t n = e.path_len;
+      uint64_t T = first;
+      bool acc = nullable != 0;
+      uint32_t j = 0;
+      for (uint32_t k = 0; k < n; k++) {
+        const uint32_t c = s[k];
+        if (c == '/') {
+          if (j < 63) mask |= (uint64_t)acc << j;
+          j++;
+        }
+        if (!T) {  // dead for good: only the '/' are still counted
+          acc = false;
+          continue;
+        }
+        uint64_t S = T & lds[glob_accept_slot(c)];
+        acc = (S & last) != 0;
+        T = 0;
+        while (S) {
+          T |= lds[__builtin_ctzll(S)];
+          S &= S - 1;
+        }
+      }
+      if (n && s[n - 1] != '/') mask |= (uint64_t)acc << 63;
+      if (j > 63) atomicOr(bad, (uint32_t)kSrcTooDeep);
+    }
+    masks[i] = mask;
+  }
+}
+
+// The predicate on the directory s[0, k + 1) that ends at the j-th '/' of input entry i's path
+// (mk: the entry's glob mask, under kSrcGlobMasks).
+PFS_DEV bool src_dir_selected(const SrcPred& pr, const uint8_t* s, uint32_t k, uint32_t j,
+                              uint64_t mk) {
+  if (pr.glob != kSrcGlobMasks) return src_selected(pr, s, k + 1);
+  return (mk & (j < 63 ? (2ull << j) - 1 : ~0ull)) != 0;
+}
+
+// PFSCDC_INFO_MATCH of the output entry s[0, len): own = its own bit of the glob mask
+PFS_DEV uint32_t src_match(const SrcPred& pr, uint32_t len, bool own) {
+  if (pr.glob == kSrcGlobMasks) return own ? PFSCDC_INFO_MATCH : 0;
+  return pr.glob == kSrcGlobRoot && len == 1 ? PFSCDC_INFO_MATCH : 0;
+}
+
 // What input entry i emits, *lcp its common prefix with the entry before, *bad |= SrcBad.
 PFS_DEV MrgCount src_item(const RtarList& in, const SrcPred& pr, uint64_t i, uint32_t* bad,
                           uint32_t* lcp) {
@@ -3485,6 +3564,25 @@ PFS_DEV MrgCount src_item(const RtarList& in, const SrcPred& pr, uint64_t i, uin
     bool same;
     if (!src_follows(in, i, e, bad, lcp, &same)) return c;
     if (same && n && s[n - 1] == '/') *bad |= kSrcDirTwice;
+  }
+  if (pr.glob == kSrcGlobMasks) {  // the masks in place of the predicate
+    const uint64_t mk = pr.masks[i];
+    uint32_t j = 0;
+    for (uint32_t k = 0; k < *lcp; k++) j += s[k] == '/';
+    for (uint32_t k = *lcp; k + 1 < n; k++) {
+      if (s[k] != '/') continue;
+      if (src_dir_selected(pr, s, k, j, mk)) {
+        c.emit++;
+        c.blob += (uint64_t)k + 4;
+      }
+      j++;
+    }
+    if (mk) {
+      c.emit++;
+      c.recs = e.count;
+      c.blob += (uint64_t)n + e.tag_len + e.last_path_len + 3;
+    }
+    return c;
   }
   for (uint32_t k = *lcp; k + 1 < n; k++)
     if (s[k] == '/' && src_selected(pr, s, k + 1)) {
@@ -3528,9 +3626,11 @@ __global__ __launch_bounds__(kIdxBlock) void src_fill_kernel(
     const uint32_t n = e.path_len;
     uint32_t depth = 0;  // the '/' in s[0, k): a path's depth is that of its bytes but the last
     for (uint32_t k = 0; k < lcp; k++) depth += s[k] == '/';
+    // under a glob the '/' at k is the path's depth-th, and bit depth of the mask is its own
+    const uint64_t mk = pr.glob == kSrcGlobMasks ? pr.masks[i] : 0;
     for (uint32_t k = lcp; k + 1 < n; k++) {
       if (s[k] != '/') continue;
-      if (src_selected(pr, s, k + 1)) {  // dirFile.Index(): Index{Path: dir, File: {}}
+      if (src_dir_selected(pr, s, k, depth, mk)) {  // dirFile.Index(): Index{Path: dir, File: {}}
         pfscdc_index_entry o;
         o.path_off = at;
         at = put_str(blob, at, (const char*)s, k + 1);
@@ -3548,7 +3648,8 @@ __global__ __launch_bounds__(kIdxBlock) void src_fill_kernel(
         meta[oi] = SrcMeta{kSrcDir, depth, 0};
         infos[oi].size = 0;
         infos[oi].type = PFSCDC_FILE_TYPE_DIR;
-        infos[oi].flags = src_child(pr, s, k + 1);
+        infos[oi].flags =
+            src_child(pr, s, k + 1) | src_match(pr, k + 1, depth < 63 && (mk >> depth & 1));
         sizes[oi] = MrgCount{0, 0, 0};
         atomicMax(maxdepth, depth);
         atomicAdd(maxdepth + 1, 1u);  // directories inserted
@@ -3556,7 +3657,7 @@ __global__ __launch_bounds__(kIdxBlock) void src_fill_kernel(
       }
       depth++;
     }
-    if (!src_selected(pr, s, n)) continue;
+    if (pr.glob == kSrcGlobMasks ? mk == 0 : !src_selected(pr, s, n)) continue;
     pfscdc_index_entry o = e;
     put_entry_strings(o, in.blob, blob, at);
     o.first = (uint32_t)first;
@@ -3566,7 +3667,8 @@ __global__ __launch_bounds__(kIdxBlock) void src_fill_kernel(
     meta[oi] = SrcMeta{(uint32_t)i, depth, 0};
     infos[oi].size = dir ? 0 : e.size_bytes;
     infos[oi].type = dir ? PFSCDC_FILE_TYPE_DIR : PFSCDC_FILE_TYPE_FILE;
-    infos[oi].flags = src_child(pr, s, n);
+    infos[oi].flags =
+        src_child(pr, s, n) | src_match(pr, n, mk >> (dir ? (depth < 63 ? depth : 0) : 63) & 1);
     sizes[oi] = MrgCount{0, 0, dir ? 0 : (uint64_t)e.size_bytes};
     atomicMax(maxdepth, depth);
   }
@@ -3678,6 +3780,15 @@ __global__ __launch_bounds__(kIdxBlock) void src_scatter_kernel(
     const pfscdc_segment* sg = &segs[level < 0 ? o : base[3 * o + 1]];
     for (int k = 0; k < 32; k++) infos[o].hash[k] = sg->hash[k];
   }
+}
+
+hipError_t launch_src_glob(const RtarList& in, const uint64_t* prog, uint64_t first, uint64_t last,
+                           bool nullable, uint64_t* masks, uint32_t* bad, int num_cus,
+                           hipStream_t st) {
+  if (in.n == 0) return hipSuccess;
+  src_glob_kernel<<<merge_grid(in.n, num_cus), kIdxBlock, 0, st>>>(in, prog, first, last,
+                                                                   nullable ? 1u : 0u, masks, bad);
+  return hipGetLastError();
 }
 
 hipError_t launch_src_count(const RtarList& in, const SrcPred& pr, MrgCount* cnt, uint32_t* bad,

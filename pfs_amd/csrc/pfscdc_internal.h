@@ -467,7 +467,14 @@ hipError_t launch_rtar_chunks(pfscdc_slice* slices, uint64_t m, const uint32_t* 
 struct SrcPred {  // SrcArg (source.h) with its strings on the device
   const char *name, *dir;
   uint32_t name_len, dir_len;
-  uint32_t all, exclude_dir, child_flag, reserved;
+  uint32_t all, exclude_dir, child_flag;
+  uint32_t glob;          // SrcGlob: 0 for the four kinds of the shared form
+  const uint64_t* masks;  // kSrcGlobMasks: launch_src_glob's mask per input entry
+};
+enum SrcGlob : uint32_t {
+  kSrcGlobNone = 0,
+  kSrcGlobMasks = 1,  // selection and PFSCDC_INFO_MATCH from masks[]
+  kSrcGlobRoot = 2,   // glob == "/": all is set, PFSCDC_INFO_MATCH on "/" alone
 };
 enum SrcBad : uint32_t {  // what the count pass found in the input
   kSrcUnordered = 1,  // not in (path, tag) order                    } the host arm
@@ -475,7 +482,16 @@ enum SrcBad : uint32_t {  // what the count pass found in the input
   kSrcDirTwice = 4,   // one directory path twice                    } call
   kSrcMalformed = 8,  // strings or DataRefs outside the arrays: PFSCDC_EINVAL
   kSrcNotLevel0 = 16, // an entry with a Range: PFSCDC_EINVAL
+  kSrcTooDeep = 32,   // (launch_src_glob) a path of more than 63 '/': the host arm takes the call
 };
+// The glob pass, ahead of the count pass.  prog: GlobProgram's follow[64] and accept_byte[256]
+// (glob.h) on the device.  masks[i] for input entry i: bit j = the bytes before the j-th '/' of
+// its path are accepted (j = 0: the root, the empty string; a directory's own final '/' is one of
+// them), bit 63 = a path that does not end in '/' is accepted as a whole; 0 for an entry outside
+// the arrays.  *bad |= kSrcTooDeep.  Each path is walked once.
+hipError_t launch_src_glob(const RtarList& in, const uint64_t* prog, uint64_t first, uint64_t last,
+                           bool nullable, uint64_t* masks, uint32_t* bad, int num_cus,
+                           hipStream_t st);
 constexpr uint32_t kSrcDir = 0xffffffffu;  // SrcMeta::src of an inserted directory
 struct SrcMeta {  // per output entry
   uint32_t src;    // the input entry it is, or kSrcDir

@@ -13,6 +13,7 @@
 //   server/pfs/server/driver_file.go:173-385         the predicates of getFile, inspectFile,
 //                                                    listFile, walkFile, diffFile
 //   server/pfs/server/paths.go:22-60                 globMatchFunction, pathIsChild, cleanPath
+//   server/pfs/server/driver_file.go:284-308         globFile's second match, over the same stream
 #include "source.h"
 
 #include <cstdlib>
@@ -182,6 +183,10 @@ int source_arg(int kind, const char* arg, SrcArg* out, std::string* err) {
       out->dir = a + "/";
       out->all = a == "/";  // mf("/") holds, "/" comes first and every path has its prefix
       return PFSCDC_OK;
+    case PFSCDC_SRC_GLOB:  // getFile / globFile: globMatchFunction(cleanPath(arg))
+      out->name = a;
+      out->all = a == "/";
+      return glob_parse(a, &out->glob, err);
     default:
       *err = "an unknown Source predicate";
       return PFSCDC_EINVAL;
@@ -191,6 +196,15 @@ int source_arg(int kind, const char* arg, SrcArg* out, std::string* err) {
 std::string source_not_found(const SrcArg& a) {
   return "file " + (a.name.empty() ? std::string("/") : a.name) + " not found";
 }
+
+// NewErrOnEmpty: getFile (literal or glob), and inspect / walk below the root (walkFile forgives
+// it for the root); never a side of diffFile, whose missing path is an empty side
+bool source_errs_on_empty(const SrcArg& a) {
+  return a.kind == PFSCDC_SRC_GET || a.kind == PFSCDC_SRC_GLOB ||
+         (a.kind == PFSCDC_SRC_SUBTREE && !a.name.empty());
+}
+
+void source_host_set_error(const std::string& text) { t_host_error = text; }
 
 namespace {
 
@@ -210,6 +224,7 @@ bool predicate(const SrcArg& a, const std::string& path) {
       if (path == a.dir) return false;  // the directory itself is not listed
       if (path == a.name) return true;
       return has_prefix(path, a.dir);
+    case PFSCDC_SRC_GLOB: return glob_mf(a.glob, path);
     default: {  // globMatchFunction of a literal glob
       if (path == "/" && a.name == "/") return true;
       return trim_slashes(path, false, true) == a.name;
@@ -341,10 +356,10 @@ int source_host(const List& in, const SrcArg& a, const uint8_t* leaf, List* out,
       emit(std::string(p.p, p.n), (int64_t)i);
     }
   }
-  // ---- indexFilter.Iterate (transforms.go:31-49); getFile alone passes full
+  // ---- indexFilter.Iterate (transforms.go:31-49); getFile and globFile alone pass full
   std::vector<Item> selected;
   {
-    const bool full = a.kind == PFSCDC_SRC_GET;
+    const bool full = a.kind == PFSCDC_SRC_GET || a.kind == PFSCDC_SRC_GLOB;
     std::string dir;
     for (const Item& f : inserted) {
       if (full) {
@@ -371,6 +386,8 @@ int source_host(const List& in, const SrcArg& a, const uint8_t* leaf, List* out,
     r.size = fi.size;
     r.type = is_dir(f.path) ? PFSCDC_FILE_TYPE_DIR : PFSCDC_FILE_TYPE_FILE;
     r.flags = a.child_flag && path_is_child(a.name, clean_path(f.path)) ? PFSCDC_INFO_CHILD : 0u;
+    // globFile's second mf(fi.File.Path) (driver_file.go:284-308)
+    if (a.kind == PFSCDC_SRC_GLOB && predicate(a, f.path)) r.flags |= PFSCDC_INFO_MATCH;
     infos->push_back(r);
     if (out->entries.size() >= 0xffffffffull) {
       *err = "more than 2^32 - 1 entries";
@@ -396,9 +413,8 @@ int source_host(const List& in, const SrcArg& a, const uint8_t* leaf, List* out,
     out->entries.push_back(e);
   }
   if (ndirs_out) *ndirs_out = ndirs;
-  // ---- NewErrOnEmpty (getFile, inspectFile, walkFile; walkFile forgives it for the root)
-  if (selected.empty() &&
-      (a.kind == PFSCDC_SRC_GET || (a.kind == PFSCDC_SRC_SUBTREE && !a.name.empty()))) {
+  // ---- NewErrOnEmpty
+  if (selected.empty() && source_errs_on_empty(a)) {
     *err = source_not_found(a);
     return PFSCDC_ENOTFOUND;
   }

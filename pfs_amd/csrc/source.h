@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "glob.h"
 #include "index_list.h"
 #include "paths.h"
 
@@ -20,14 +21,20 @@ namespace pfscdc {
 // GET(g): name = g, dir = g + "/" (TrimRight(path, "/") == g is path == g or path == g + "/" for a
 // clean path, and the `full` filter's dir state, set at g + "/", passes HasPrefix(path, g + "/"):
 // stateless, because the inserter puts g + "/" in front of everything below it); g == "/": all.
+// GLOB(g) is outside that form: name = g, glob = g parsed, and the predicate is glob_mf (glob.h)
+// under the `full` filter; g == "/": all, as GET's.
 struct SrcArg {
   int kind = 0;
   std::string name, dir;
   bool all = false, exclude_dir = false, child_flag = false;
+  Glob glob;
 };
-// PFSCDC_EUNSUPPORTED (a glob pattern) / PFSCDC_EINVAL (an unknown kind) with *err set
+// PFSCDC_EUNSUPPORTED (GET: a glob pattern; GLOB: extglob) / PFSCDC_EINVAL (an unknown kind; GLOB:
+// a glob that does not compile) with *err set
 int source_arg(int kind, const char* arg, SrcArg* out, std::string* err);
 std::string source_not_found(const SrcArg& a);  // NewErrOnEmpty's text
+bool source_errs_on_empty(const SrcArg& a);     // whether the RPC wraps its stream in NewErrOnEmpty
+void source_host_set_error(const std::string& text);  // what pfscdc_source_host_error returns
 
 // pfscdc_source_host over the internal types; *err names an error, *ndirs (nullable) = the
 // directory entries the inserter made that the filter selected

@@ -12,12 +12,6 @@ namespace {
 using namespace pfscdc;
 using List = pfscdc_index_list;
 
-// NewErrOnEmpty: getFile, and inspect / walk below the root; never a side of diffFile
-// (PFSCDC_SRC_DIFF), whose missing path is an empty side
-bool errs_on_empty(const SrcArg& a) {
-  return a.kind == PFSCDC_SRC_GET || (a.kind == PFSCDC_SRC_SUBTREE && !a.name.empty());
-}
-
 // The host arm: the list comes to the host, pfscdc_source_host's body runs, its result goes back.
 int host_arm(pfscdc_ctx* ctx, const pfscdc_dev_list& in, const SrcArg& a, const uint8_t* leaf,
              int leaf_on_device, pfscdc_source** out) {
@@ -57,12 +51,21 @@ int source_open(pfscdc_ctx* ctx, const pfscdc_dev_list& in, int kind, const char
   if (int rc = source_arg(kind, arg, &a, &err)) return ctx_fail(ctx, rc, err);
   PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
   if (knob(Knob::Source) == 0) return host_arm(ctx, in, a, leaf, leaf_on_device, out);
+  // a glob but "/" (all, with PFSCDC_INFO_MATCH on "/" alone) runs as a position automaton
+  const bool automaton = kind == PFSCDC_SRC_GLOB && !a.all;
+  std::unique_ptr<GlobProgram> prog;
+  if (automaton) {
+    prog.reset(new GlobProgram());
+    glob_compile(a.glob, prog.get());
+    // more positions than one uint64_t holds: no device program
+    if (prog->positions > 64) return host_arm(ctx, in, a, leaf, leaf_on_device, out);
+  }
   hipStream_t s = ctx_stream(ctx);
   const int cus = ctx_num_cus(ctx);
   const RtarList l = view(in);
   Clock clk;
-  // ---- insert and select: count, prefix sums
-  GuardMem d_arg, d_cnt, d_base, d_flags;
+  // ---- insert and select: (the glob masks,) count, prefix sums
+  GuardMem d_arg, d_cnt, d_base, d_flags, d_prog, d_masks;
   Guards g;
   PFS_HIP(ctx, d_arg.alloc(a.name.size() + a.dir.size(), s));
   PFS_HIP(ctx, d_cnt.alloc(sizeof(MrgCount) * l.n, s));
@@ -78,8 +81,19 @@ int source_open(pfscdc_ctx* ctx, const pfscdc_dev_list& in, int kind, const char
     st.n[6] += both.size();
   }
   PFS_HIP(ctx, hipMemsetAsync(d_flags.p, 0, 4 * sizeof(uint32_t), s));
+  if (automaton) {
+    PFS_HIP(ctx, d_prog.alloc(sizeof prog->table, s));
+    PFS_HIP(ctx, d_masks.alloc(sizeof(uint64_t) * l.n, s));
+    g.add(d_masks);
+    PFS_HIP(ctx, hipMemcpyAsync(d_prog.p, prog->table, sizeof prog->table, hipMemcpyHostToDevice, s));
+    st.n[6] += sizeof prog->table;
+    PFS_HIP(ctx, launch_src_glob(l, d_prog.as<uint64_t>(), prog->first, prog->last, prog->nullable,
+                                 d_masks.as<uint64_t>(), d_flags.as<uint32_t>(), cus, s));
+  }
+  const uint32_t glob = automaton ? kSrcGlobMasks : kind == PFSCDC_SRC_GLOB ? kSrcGlobRoot : kSrcGlobNone;
   const SrcPred pr{d_arg.as<char>(), d_arg.as<char>() + a.name.size(), (uint32_t)a.name.size(),
-                   (uint32_t)a.dir.size(), a.all, a.exclude_dir, a.child_flag, 0};
+                   (uint32_t)a.dir.size(), a.all, a.exclude_dir, a.child_flag, glob,
+                   d_masks.as<uint64_t>()};
   PFS_HIP(ctx, launch_src_count(l, pr, d_cnt.as<MrgCount>(), d_flags.as<uint32_t>(), cus, s));
   PFS_HIP(ctx, launch_merge_scan(d_cnt.as<MrgCount>(), l.n, d_base.as<uint64_t>(), s));
   uint64_t totals[3] = {0, 0, 0};
@@ -99,7 +113,7 @@ int source_open(pfscdc_ctx* ctx, const pfscdc_dev_list& in, int kind, const char
   const uint64_t m = totals[0], nr = totals[1];
   if (m > 0xffffffffull) return ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "more than 2^32 - 1 entries");
   if (nr > l.nr) return ctx_fail(ctx, PFSCDC_EHIP, "source: the counts exceed the input");
-  if (m == 0 && errs_on_empty(a)) return ctx_fail(ctx, PFSCDC_ENOTFOUND, source_not_found(a));
+  if (m == 0 && source_errs_on_empty(a)) return ctx_fail(ctx, PFSCDC_ENOTFOUND, source_not_found(a));
   // ---- fill: entries, strings, DataRefs; per output entry its source, depth, type and size
   OutList o;
   GuardMem d_copy, d_meta, d_infos, d_sizes, d_sbase;
@@ -250,6 +264,42 @@ int pfscdc_source_free(pfscdc_source* s) {
   if (!s) return PFSCDC_OK;
   (void)hipSetDevice(s->device);
   delete s;
+  return PFSCDC_OK;
+}
+
+int pfscdc_debug_glob_masks(pfscdc_ctx* ctx, const pfscdc_dev_list* list, const char* glob,
+                            uint64_t* masks, uint32_t* bad) {
+  if (!ctx || !list || !glob || !bad || (list->n && !masks)) return PFSCDC_EINVAL;
+  if (list->device != pfscdc::ctx_device(ctx))
+    return pfscdc::ctx_fail(ctx, PFSCDC_EINVAL, "a resident list of another device");
+  pfscdc::Glob g;
+  std::string err;
+  if (int rc = pfscdc::glob_parse(pfscdc::clean_path(glob), &g, &err))
+    return pfscdc::ctx_fail(ctx, rc, err);
+  std::unique_ptr<pfscdc::GlobProgram> prog(new pfscdc::GlobProgram());
+  pfscdc::glob_compile(g, prog.get());
+  if (prog->positions > 64)
+    return pfscdc::ctx_fail(ctx, PFSCDC_EUNSUPPORTED, "a glob of more than 64 positions");
+  hipStream_t s = pfscdc::ctx_stream(ctx);
+  PFS_HIP(ctx, hipSetDevice(list->device));
+  pfscdc::GuardMem d_prog, d_masks, d_bad;
+  pfscdc::Guards gd;
+  PFS_HIP(ctx, d_prog.alloc(sizeof prog->table, s));
+  PFS_HIP(ctx, d_masks.alloc(sizeof(uint64_t) * list->n, s));
+  PFS_HIP(ctx, d_bad.alloc(sizeof(uint32_t), s));
+  gd.add(d_masks);
+  gd.add(d_bad);
+  PFS_HIP(ctx, hipMemcpyAsync(d_prog.p, prog->table, sizeof prog->table, hipMemcpyHostToDevice, s));
+  PFS_HIP(ctx, hipMemsetAsync(d_bad.p, 0, sizeof(uint32_t), s));
+  PFS_HIP(ctx, pfscdc::launch_src_glob(pfscdc::view(*list), d_prog.as<uint64_t>(), prog->first,
+                                       prog->last, prog->nullable, d_masks.as<uint64_t>(),
+                                       d_bad.as<uint32_t>(), pfscdc::ctx_num_cus(ctx), s));
+  if (list->n)
+    PFS_HIP(ctx, hipMemcpyAsync(masks, d_masks.p, sizeof(uint64_t) * list->n, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipMemcpyAsync(bad, d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, gd.fetch(s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
+  if (!gd.ok()) return pfscdc::ctx_fail(ctx, PFSCDC_EHIP, "glob: the kernel wrote past its array");
   return PFSCDC_OK;
 }
 

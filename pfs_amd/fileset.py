@@ -597,6 +597,69 @@ def source_host(lst: Optional[IndexList], kind: int, arg: str = "", leaf=None):
     return res, got
 
 
+GLOB_BYTES = "*?[]{}!()@+^\\"
+
+
+def _glob_kind(p: str) -> int:
+    """PFSCDC_SRC_GLOB if ``cleanPath(p)`` holds a glob byte, else PFSCDC_SRC_GET."""
+    q = clean(p, False)
+    return _lib.SRC_GLOB if any(c in q for c in GLOB_BYTES) else _lib.SRC_GET
+
+
+def _glob_error(rc: int):
+    return _lib.PfsCdcError(rc, _lib.load().pfscdc_source_host_error().decode("utf-8", "replace"))
+
+
+def glob_match(glob: str, path: str) -> bool:
+    """pfscdc_glob_match: ``globMatchFunction(cleanPath(glob))(path)``, the backtracking matcher
+    that is the specification of the dialect (no GPU call).  PfsCdcError for a glob that does not
+    compile (PFSCDC_EINVAL) or that holds extglob (PFSCDC_EUNSUPPORTED)."""
+    hit = C.c_int(0)
+    rc = _lib.load().pfscdc_glob_match(glob.encode("utf-8", "surrogateescape"),
+                                       path.encode("utf-8", "surrogateescape"), C.byref(hit))
+    if rc:
+        raise _glob_error(rc)
+    return bool(hit.value)
+
+
+def glob_literal_prefix(glob: str) -> str:
+    """pfscdc_glob_literal_prefix: ``globLiteralPrefix(cleanPath(glob))``."""
+    out = C.create_string_buffer(len(glob.encode("utf-8", "surrogateescape")) + 8)
+    rc = _lib.load().pfscdc_glob_literal_prefix(glob.encode("utf-8", "surrogateescape"), out,
+                                                len(out))
+    if rc:
+        raise _lib.PfsCdcError(rc, "pfscdc_glob_literal_prefix")
+    return out.value.decode("utf-8", "surrogateescape")
+
+
+def glob_program(glob: str) -> dict:
+    """pfscdc_debug_glob_program (a test hook): the position automaton of ``cleanPath(glob)``
+    as the device stages it: ``follow`` (64) and ``accept_byte`` (256) as uint64 arrays,
+    ``first``, ``last``, ``nullable`` and ``positions``."""
+    out = (C.c_uint64 * 324)()
+    rc = _lib.load().pfscdc_debug_glob_program(glob.encode("utf-8", "surrogateescape"), out)
+    if rc:
+        raise _glob_error(rc)
+    w = np.frombuffer(out, dtype=np.uint64).copy()
+    return {"follow": w[:64], "accept_byte": w[64:320], "first": int(w[320]), "last": int(w[321]),
+            "nullable": bool(w[322]), "positions": int(w[323])}
+
+
+def glob_masks(chunker, lst: "DevIndexList", glob: str):
+    """pfscdc_debug_glob_masks (a test hook): the glob kernel alone over a resident list;
+    ``(masks, bad)`` with one uint64 per entry."""
+    n = len(lst)
+    masks = np.zeros(max(1, n), dtype=np.uint64)
+    bad = C.c_uint32(0)
+    rc = chunker.lib.pfscdc_debug_glob_masks(
+        chunker.ctx, lst._p, glob.encode("utf-8", "surrogateescape"),
+        masks.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(bad))
+    if rc:
+        msg = chunker.lib.pfscdc_last_error(chunker.ctx)
+        raise _lib.PfsCdcError(rc, msg.decode("utf-8", "replace") if msg else "")
+    return masks[:n], int(bad.value)
+
+
 class _BorrowedDevList(DevIndexList):
     """A source's list: owned by the source, which it keeps alive."""
 
@@ -946,7 +1009,8 @@ class FileSet:
         finally:
             c.close()
 
-    def _infos(self, kind: int, arg: str, children: bool = False) -> list:
+    def _infos(self, kind: int, arg: str, only: int = 0) -> list:
+        """The source's FileInfos; ``only``: those with this PFSCDC_INFO_* flag."""
         src = self._source(kind, arg)
         try:
             raw, infos = src.list.download().raw(), src.infos()
@@ -955,7 +1019,7 @@ class FileSet:
         return [FileInfo(d["path"].decode("utf-8", "surrogateescape"),
                          d["tag"].decode("utf-8", "surrogateescape"), t, size, h)
                 for d, (h, size, t, flags) in zip(raw, infos)
-                if not children or flags & _lib.INFO_CHILD]
+                if not only or flags & only]
 
     def walk_file(self, p: str = "") -> list:
         """``walkFile``: the ``FileInfo`` of ``p`` and of everything below it, directories
@@ -966,7 +1030,7 @@ class FileSet:
     def list_file(self, p: str = "") -> list:
         """``listFile``: the ``FileInfo`` of the immediate children of directory ``p`` (of the
         file ``p`` itself, if it is one)."""
-        return self._infos(_lib.SRC_LIST, p, children=True)
+        return self._infos(_lib.SRC_LIST, p, only=_lib.INFO_CHILD)
 
     def inspect_file(self, p: str = "") -> Optional[FileInfo]:
         """``inspectFile``: the ``FileInfo`` of ``p`` (the last entry with path ``p`` or
@@ -977,10 +1041,19 @@ class FileSet:
         return hits[-1] if hits else None
 
     def get_file(self, p: str) -> TarStream:
-        """``getFile`` of a literal path as ``GetFileTAR`` serves it: ``p`` (a file, or a
-        directory with everything below it) as a ``TarStream`` with one entry per entry of the
-        source, directories included.  KeyError if nothing is there."""
-        return _SourceTarStream(self._storage, self._source(_lib.SRC_GET, p))
+        """``getFile`` as ``GetFileTAR`` serves it: what the glob ``p`` matches (each a file, or
+        a directory with everything below it) as a ``TarStream`` with one entry per entry of the
+        source, directories included.  A ``p`` with none of the glob bytes names one path.
+        KeyError if nothing is there."""
+        return _SourceTarStream(self._storage, self._source(_glob_kind(p), p))
+
+    def glob_file(self, pattern: str) -> list:
+        """``globFile``: the ``FileInfo`` of every path the glob ``pattern`` matches itself; a
+        matched directory's size and hash cover everything below it.  Nothing matched is []."""
+        try:
+            return self._infos(_lib.SRC_GLOB, pattern, only=_lib.INFO_MATCH)
+        except KeyError:  # getFile's NewErrOnEmpty, which globFile does not wrap its stream in
+            return []
 
     def diff_file(self, old: Optional["FileSet"], path: str = "",
                   old_path: Optional[str] = None) -> list:

@@ -85,8 +85,15 @@ upload).  The arms' arrays are compared.  One copy_file of a directory of 1,024 
 whose chunks pass by reference is recorded beside them.  Writes
 profiles/r7/read_path/copy.json.
 
+--glob: GlobFile (pfscdc_source_open with PFSCDC_SRC_GLOB) over resident lists of 65,536 files of
+4 KiB and of --files files of 256 B at fan-out 64, five globs ("/**", "/*/*/f1*" and "/**.2",
+which select nothing in this tree, "/b/*/0?/**" and "/**1"), the device arm (PFSCDC_SOURCE=1) and
+the host arm (0) alternating call by call, and SUBTREE("") on the device arm beside them.  Per
+arm: median, min and max of each stage's and the whole call's wall time.  The arms' first results
+are compared array for array and info for info.  Writes profiles/r25/glob/glob.json.
+
 usage: python tools/read_bench.py [--tar | --index | --merge | --compact | --resident | --source
-                                   | --diff | --copy]
+                                   | --diff | --copy | --glob]
                                   [--chunks N]
                                   [--chunk-bytes B] [--files N] [--reps R] [--warmup W]
                                   [--out PATH]"""
@@ -797,6 +804,77 @@ def source_rows(args):
     return rows
 
 
+GLOB_PATTERNS = ("/**", "/*/*/f1*", "/**.2", "/b/*/0?/**", "/**1")
+
+
+def glob_rows(args):
+    """--glob: PFSCDC_SRC_GLOB over a resident list of 65,536 and of --files files laid out
+    over a tree of fan-out 64 (/b/AA/BB/CC/fNNNNNNN), the device arm (PFSCDC_SOURCE=1: the glob
+    kernel ahead of the count pass) and the host arm (0) alternating call by call.  "/**"
+    selects everything below the root; "/*/*/f1*" and "/**.2" select nothing in this tree (the
+    whole cost is the predicate; both arms answer not-found); "/b/*/0?/**" selects ten of the 64
+    second-level directories of each top one whole and "/**1" a tenth of the files, as orphans,
+    and of the directories.  SUBTREE("") on the device arm is timed beside them, for comparison
+    with the commit before.  In the first round of every pattern the device result is compared
+    with the host arm's, array for array and info for info."""
+    import time
+
+    from pfs_amd import fileset as PF
+    rows = []
+    keys = ["select_ms", "tree_ms", "leaf_ms", "levels_ms", "wall_ms"]
+    for nfiles, fbytes in [(65536, 4096)] + ([(args.files, 256)] if args.files != 65536 else []):
+        lst = source_list(nfiles, fbytes, False, nfiles)
+        c = Chunker(ChunkParams(), 0)
+        dev = PF.DevIndexList.upload(c, lst)
+        for kind, arg in [(_lib.SRC_GLOB, g) for g in GLOB_PATTERNS] + [(_lib.SRC_SUBTREE, "")]:
+            arms = (1, 0) if kind == _lib.SRC_GLOB else (1,)
+            runs = {arm: [] for arm in arms}
+            last = {}
+            for i in range(args.warmup + args.reps):
+                for arm in arms:
+                    _lib.set_knob("PFSCDC_SOURCE", arm)
+                    t0 = time.perf_counter()
+                    try:
+                        src = PF.source_open(c, dev, kind, arg)
+                    except KeyError:
+                        src = None
+                    wall = (time.perf_counter() - t0) * 1e3
+                    stats = PF.last_source_stats(c)
+                    if src is not None and stats["device"] != arm:
+                        raise SystemExit("read_bench: the wrong arm ran")
+                    if src is None:
+                        last[arm] = None
+                    else:
+                        if i == 0:
+                            got = src.list.download(c)
+                            last[arm] = (list_arrays(got), src.infos(c))
+                            got.free()
+                        src.free()
+                    if i == 0 and arm == 0 and last[0] != last[1]:
+                        raise SystemExit("read_bench: the device arm's result differs from the host arm's")
+                    if i >= args.warmup:
+                        stats["wall_ms"] = wall
+                        runs[arm].append(stats)
+            row = {"files": nfiles, "file_bytes": fbytes, "layout": "fanout64",
+                   "predicate": "GLOB" if kind == _lib.SRC_GLOB else "SUBTREE", "arg": arg,
+                   "reps": args.reps, "warmup": args.warmup, "found": last[1] is not None,
+                   "device_equals_host": len(arms) == 2}
+            for arm in arms:
+                r = runs[arm]
+                name = "device" if arm else "host"
+                row[name] = {k: {"median": round(statistics.median(x[k] for x in r), 3),
+                                 "min": round(min(x[k] for x in r), 3),
+                                 "max": round(max(x[k] for x in r), 3)} for k in keys}
+                row[name].update({k: r[0][k] for k in ("entries_in", "entries_out", "dirs_inserted",
+                                                       "levels", "hash_launches")})
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        _lib.set_knob("PFSCDC_SOURCE", _lib.knob_info()["PFSCDC_SOURCE"][2])
+        dev.free()
+        c.close()
+    return rows
+
+
 def copy_rows(args):
     """--copy: pfscdc_dev_list_copy_map over a resident list whose first half lies under /b and
     whose second half under /c, src = /b: the device arm (PFSCDC_COPY_MAP=1) and the host arm (0)
@@ -914,6 +992,7 @@ def main():
     ap.add_argument("--source", action="store_true")
     ap.add_argument("--diff", action="store_true")
     ap.add_argument("--copy", action="store_true")
+    ap.add_argument("--glob", action="store_true")
     ap.add_argument("--files", type=int, default=1 << 20)
     ap.add_argument("--tar", action="store_true")
     ap.add_argument("--chunks", type=int, default=1024)
@@ -945,6 +1024,16 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/read_bench.py --source",
+                       "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
+            f.write("\n")
+        return
+    if args.glob:
+        if args.out == os.path.join(ROOT, "profiles", "r7", "read_path", "read_bench.json"):
+            args.out = os.path.join(ROOT, "profiles", "r25", "glob", "glob.json")
+        rows = glob_rows(args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/read_bench.py --glob",
                        "device": torch.cuda.get_device_name(0), "shapes": rows}, f, indent=1)
             f.write("\n")
         return
