@@ -2,18 +2,31 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -pthread
-SRC := pfs_amd/csrc/cdc_kernels.hip pfs_amd/csrc/pfscdc.cpp pfs_amd/csrc/writer.cpp pfs_amd/csrc/tar.cpp pfs_amd/csrc/index.cpp pfs_amd/csrc/resident.cpp pfs_amd/csrc/index_decode.cpp pfs_amd/csrc/index_merge.cpp pfs_amd/csrc/fileset.cpp pfs_amd/csrc/group.cpp pfs_amd/csrc/gorand.cpp pfs_amd/csrc/knobs.cpp pfs_amd/csrc/glob.cpp pfs_amd/csrc/source.cpp pfs_amd/csrc/source_dev.cpp pfs_amd/csrc/diff.cpp pfs_amd/csrc/diff_dev.cpp pfs_amd/csrc/copy_map.cpp pfs_amd/csrc/copy_map_dev.cpp
-HDR := include/pfscdc.h pfs_amd/csrc/pfscdc_internal.h pfs_amd/csrc/index_parse.h pfs_amd/csrc/index_list.h pfs_amd/csrc/dev_list.h pfs_amd/csrc/dev_pass.h pfs_amd/csrc/source.h pfs_amd/csrc/glob.h pfs_amd/csrc/diff.h pfs_amd/csrc/paths.h pfs_amd/csrc/copy_map.h
+# one object per source, JOBS of them at a time (a make that ignores the line builds serially);
+# the line also overrides a -j on the command line: JOBS=n is the knob
+JOBS ?= 8
+MAKEFLAGS += -j$(JOBS)
+SRC := $(addprefix pfs_amd/csrc/,cdc_kernels.hip list_kernels.hip pfscdc.cpp writer.cpp tar.cpp \
+  index.cpp resident.cpp index_decode.cpp index_merge.cpp fileset.cpp group.cpp gorand.cpp \
+  knobs.cpp glob.cpp source.cpp source_dev.cpp diff.cpp diff_dev.cpp copy_map.cpp copy_map_dev.cpp)
+HDR := include/pfscdc.h $(addprefix pfs_amd/csrc/,pfscdc_internal.h list_kernels.h index_parse.h \
+  index_list.h dev_list.h dev_pass.h source.h glob.h diff.h paths.h copy_map.h)
+OBJ := $(patsubst pfs_amd/csrc/%,build/obj/%.o,$(SRC))
 
 all: pfs_amd/libpfscdc.so oracle/_build/liboracle.so
 
-pfs_amd/libpfscdc.so: $(SRC) $(HDR)
-	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -shared -x hip $(filter %.hip %.cpp,$(SRC)) -o $@
+build/obj/%.o: pfs_amd/csrc/% $(HDR)
+	@mkdir -p $(@D)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -x hip -c $< -o $@
+
+pfs_amd/libpfscdc.so: $(OBJ)
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -shared $(OBJ) -o $@
 
 oracle/_build/liboracle.so: oracle/cdc_oracle.c oracle/Makefile
 	$(MAKE) -C oracle
 
 clean:
+	rm -rf build/obj
 	rm -f pfs_amd/libpfscdc.so oracle/_build/liboracle.so
 
 .PHONY: all clean

@@ -1043,6 +1043,12 @@ int pfscdc_last_source_timings(pfscdc_ctx* ctx, float out[4]);
  * glob of more than 64 positions; compile errors as pfscdc_glob_match's (pfscdc_last_error). */
 int pfscdc_debug_glob_masks(pfscdc_ctx* ctx, const pfscdc_dev_list* list, const char* glob,
                             uint64_t* masks, uint32_t* bad);
+/* Test hook: a prefix-sum kernel of the list passes alone.  in: n < 2^32 host records of kind 0
+ * {uint32 records, uint32 blob bytes} (2 columns), 1 {uint32 entries, uint32 DataRefs, uint64
+ * blob bytes} (3 columns) or 2 one uint64 <= 2^62 + 1 (1 column, the add saturating at
+ * 2^62 + 1).  out: N (n + 1) words, out[N i + c] = column c summed over the records before i,
+ * out[N n + c] the totals. */
+int pfscdc_debug_list_scan(pfscdc_ctx* ctx, int kind, const void* in, uint64_t n, uint64_t* out);
 
 /* ---- DiffFile: two Sources joined by path (src/server/pfs/server/diff.go:22-96) -----------------
  * Differ.Iterate walks sides a (the old commit; emptySource when there is none) and b (the new

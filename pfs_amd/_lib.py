@@ -84,7 +84,7 @@ EXPORTED = [
     "pfscdc_source_infos", "pfscdc_source_free", "pfscdc_last_source_stats",
     "pfscdc_last_source_timings",
     "pfscdc_glob_match", "pfscdc_glob_literal_prefix", "pfscdc_debug_glob_program",
-    "pfscdc_debug_glob_masks",
+    "pfscdc_debug_glob_masks", "pfscdc_debug_list_scan",
     "pfscdc_diff_host", "pfscdc_diff_pairs_free", "pfscdc_source_diff", "pfscdc_diff_count",
     "pfscdc_diff_pairs", "pfscdc_diff_side", "pfscdc_diff_free", "pfscdc_last_diff_stats",
     "pfscdc_last_diff_timings",
@@ -420,6 +420,7 @@ def load() -> C.CDLL:
             "pfscdc_glob_literal_prefix": (i32, [C.c_char_p, C.c_char_p, C.c_size_t]),
             "pfscdc_debug_glob_program": (i32, [C.c_char_p, P(u64)]),
             "pfscdc_debug_glob_masks": (i32, [vp, vp, C.c_char_p, P(u64), P(u32)]),
+            "pfscdc_debug_list_scan": (i32, [vp, i32, vp, u64, P(u64)]),
             "pfscdc_diff_host": (i32, [vp, P(FileInfoC), vp, P(FileInfoC), P(P(DiffPairC)),
                                        P(u64)]),
             "pfscdc_diff_pairs_free": (None, [P(DiffPairC)]),

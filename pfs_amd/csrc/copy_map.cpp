@@ -1,6 +1,6 @@
 // copy_map.cpp — CopyFile's selection and path transform on the host (pfscdc_copy_map_host): the
 // open's options, NewIndexFilter's predicate and NewIndexMapper's transform, each taken literally.
-// It is the specification the cmap_* kernels (cdc_kernels.hip §13, driven by copy_map_dev.cpp)
+// It is the specification the cmap_* kernels (list_kernels.hip §13, driven by copy_map_dev.cpp)
 // are tested against, and the arm for the lists the device refuses.  No GPU call and no HIP header
 // in this file: a stand-alone sanitizer build compiles it with index_decode.cpp and a plain C++
 // compiler.

@@ -1,5 +1,5 @@
 // copy_map_dev.cpp — CopyFile's selection and path transform over a device-resident list
-// (pfscdc_dev_list_copy_map): the driver of the cmap_* kernels (cdc_kernels.hip §13) and the
+// (pfscdc_dev_list_copy_map): the driver of the cmap_* kernels (list_kernels.hip §13) and the
 // hand-over to the host arm (copy_map.cpp).
 #include <memory>
 #include <string>

@@ -12,7 +12,7 @@
 
 #include "dev_list.h"
 #include "index_list.h"
-#include "pfscdc_internal.h"
+#include "list_kernels.h"
 
 namespace pfscdc {
 
@@ -97,7 +97,7 @@ struct Guards {
 };
 
 // The list a pass writes: the arrays its fill kernel and launch_list_copy fill at the ranges the
-// prefix sums gave (pfscdc_internal.h, "the list passes").
+// prefix sums gave (list_kernels.h, "the list passes").
 struct OutList {
   GuardMem entries, blob, drs;
   uint64_t m = 0, nr = 0, nb = 0;  // entries, DataRefs, blob bytes: the prefix sums' totals

@@ -1,5 +1,5 @@
 // diff.cpp — DiffFile on the host (pfscdc_diff_host): Differ.Iterate's two-pointer walk taken
-// literally.  It is the specification the diff_* kernels (cdc_kernels.hip §12, driven by
+// literally.  It is the specification the diff_* kernels (list_kernels.hip §12, driven by
 // diff_dev.cpp) are tested against, and the arm for the sides the device refuses.  No GPU call
 // and no HIP header in this file: a stand-alone sanitizer build compiles it with
 // index_decode.cpp and a plain C++ compiler.

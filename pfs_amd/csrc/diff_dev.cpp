@@ -1,5 +1,5 @@
 // diff_dev.cpp — DiffFile over two Sources of one device (pfscdc_source_diff): the driver of the
-// diff_* kernels (cdc_kernels.hip §12) and the hand-over to the host arm (diff.cpp).
+// diff_* kernels (list_kernels.hip §12) and the hand-over to the host arm (diff.cpp).
 #include <memory>
 #include <string>
 #include <vector>

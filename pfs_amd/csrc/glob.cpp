@@ -1,4 +1,4 @@
-// glob.cpp — the position automaton of a glob (what src_glob_kernel, cdc_kernels.hip §11, runs),
+// glob.cpp — the position automaton of a glob (what src_glob_kernel, list_kernels.hip §11, runs),
 // globLiteralPrefix, and the C entry points of the dialect.  The parser and the backtracking
 // matcher, which is the specification, are in glob.h; nothing here calls the matcher and the
 // matcher calls nothing here, so the two are held against each other as independent statements.

@@ -1,6 +1,6 @@
 // index.cpp — reading a fileset back: index.Reader.Iterate over a chunk store and
 // MergeReader.iterate (host logic; the frame walk and entry decode kernels are in
-// cdc_kernels.hip, the proto parser both sides share in index_parse.h).  Both also with a
+// list_kernels.hip, the proto parser both sides share in index_parse.h).  Both also with a
 // device-resident result (pfscdc_index_read_dev, pfscdc_index_merge_dev: the decode's and the
 // merge's output arrays become a pfscdc_dev_list, dev_list.h, instead of being copied out).
 //
@@ -274,7 +274,7 @@ int read_level(pfscdc_ctx* ctx, const pfscdc_store* store, uint32_t level, const
   return rc ? ctx_fail(ctx, rc, "more than 2^32 index records") : PFSCDC_OK;
 }
 
-// MergeReader on the device (cdc_kernels.hip §9) over ns streams.  *ran = false: the call
+// MergeReader on the device (list_kernels.hip §9) over ns streams.  *ran = false: the call
 // belongs to the host arm (a stream out of order, or more than 2^32 - 1 entries or records).
 // The output arrays are an OutList's: a kernel that wrote past what the prefix sums counted fails
 // the call.

@@ -1,7 +1,7 @@
 // index_parse.h — bounded parser of one index.Index proto (fileset/index/index.proto with
 // chunk/chunk.proto's DataRef and Ref), shared by the host specification
 // (pfscdc_index_decode_host, index_decode.cpp) and the device decode (index_count_kernel /
-// index_fill_kernel, cdc_kernels.hip).  Plain C++ with no library call, so a sanitizer build
+// index_fill_kernel, list_kernels.hip).  Plain C++ with no library call, so a sanitizer build
 // of the host side checks the very bounds logic the kernels run.
 //
 // Every read is bounded by the range the caller gives: a varint longer than 10 bytes, a nested
@@ -14,7 +14,7 @@
 
 #include "../../include/pfscdc.h"
 
-// PFSCDC_HD comes from the including file: `__host__ __device__` in cdc_kernels.hip, empty in
+// PFSCDC_HD comes from the including file: `__host__ __device__` in list_kernels.hip, empty in
 // index_list.h (host code, which a plain C++ compiler must be able to build).
 
 namespace pfscdc {

@@ -1,6 +1,6 @@
 // resident.cpp — index lists that stay on the device: the pfscdc_dev_list handle, its copies to
 // and from the host, and GetFileTAR over it (the plan and window stages of tar_plan as kernels,
-// cdc_kernels.hip §10; the read path's sibling read_slices_dev_impl is in pfscdc.cpp, the
+// list_kernels.hip §10; the read path's sibling read_slices_dev_impl is in pfscdc.cpp, the
 // batch of the runs' chunks beside StoreBatch in writer.cpp).
 #include <algorithm>
 #include <cstring>

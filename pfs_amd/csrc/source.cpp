@@ -1,6 +1,6 @@
 // source.cpp — the Source on the host (pfscdc_source_host): the directory inserter, the index
 // filter and source.Iterate's FileInfo recursion, each taken literally.  It is the specification
-// the src_* kernels (cdc_kernels.hip §11, driven by source_dev.cpp) are tested against, and the
+// the src_* kernels (list_kernels.hip §11, driven by source_dev.cpp) are tested against, and the
 // arm for the lists the device refuses.  No GPU call and no HIP header in this file: a
 // stand-alone sanitizer build compiles it with index_decode.cpp and a plain C++ compiler.
 //

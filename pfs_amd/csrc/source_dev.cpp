@@ -1,5 +1,5 @@
 // source_dev.cpp — the Source over a device-resident list (pfscdc_source_open): the driver of
-// the src_* kernels (cdc_kernels.hip §11) and the hand-over to the host arm (source.cpp).
+// the src_* kernels (list_kernels.hip §11) and the hand-over to the host arm (source.cpp).
 #include <memory>
 #include <string>
 #include <vector>
@@ -300,6 +300,26 @@ int pfscdc_debug_glob_masks(pfscdc_ctx* ctx, const pfscdc_dev_list* list, const 
   PFS_HIP(ctx, gd.fetch(s));
   PFS_HIP(ctx, hipStreamSynchronize(s));
   if (!gd.ok()) return pfscdc::ctx_fail(ctx, PFSCDC_EHIP, "glob: the kernel wrote past its array");
+  return PFSCDC_OK;
+}
+
+int pfscdc_debug_list_scan(pfscdc_ctx* ctx, int kind, const void* in, uint64_t n, uint64_t* out) {
+  static const uint64_t rec[3] = {sizeof(pfscdc::IdxCount), sizeof(pfscdc::MrgCount), 8};
+  static const uint64_t cols[3] = {2, 3, 1};
+  if (!ctx || kind < 0 || kind > 2 || !out || (n && !in) || n > 0xffffffffull)
+    return PFSCDC_EINVAL;
+  hipStream_t s = pfscdc::ctx_stream(ctx);
+  PFS_HIP(ctx, hipSetDevice(pfscdc::ctx_device(ctx)));
+  pfscdc::DevMem d_in, d_out;
+  PFS_HIP(ctx, d_in.alloc(rec[kind] * n));
+  PFS_HIP(ctx, d_out.alloc(8 * cols[kind] * (n + 1)));
+  if (n) PFS_HIP(ctx, hipMemcpyAsync(d_in.p, in, rec[kind] * n, hipMemcpyHostToDevice, s));
+  uint64_t* base = d_out.as<uint64_t>();
+  PFS_HIP(ctx, kind == 0   ? pfscdc::launch_index_scan(d_in.as<pfscdc::IdxCount>(), n, base, s)
+               : kind == 1 ? pfscdc::launch_merge_scan(d_in.as<pfscdc::MrgCount>(), n, base, s)
+                           : pfscdc::launch_rtar_scan(d_in.as<uint64_t>(), n, base, nullptr, s));
+  PFS_HIP(ctx, hipMemcpyAsync(out, d_out.p, 8 * cols[kind] * (n + 1), hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, hipStreamSynchronize(s));
   return PFSCDC_OK;
 }
 

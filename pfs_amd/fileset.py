@@ -660,6 +660,29 @@ def glob_masks(chunker, lst: "DevIndexList", glob: str):
     return masks[:n], int(bad.value)
 
 
+_LIST_SCAN_KINDS = (  # pfscdc_debug_list_scan: a record's dtype and its columns
+    (np.dtype([("ndr", "<u4"), ("blob", "<u4")]), 2),
+    (np.dtype([("emit", "<u4"), ("recs", "<u4"), ("blob", "<u8")]), 3),
+    (np.dtype("<u8"), 1),
+)
+
+
+def list_scan(chunker, kind: int, records):
+    """pfscdc_debug_list_scan (a test hook): kind's prefix-sum kernel of the list passes alone over
+    ``records`` (``_LIST_SCAN_KINDS[kind]``'s dtype); a uint64 array of shape (n + 1, columns),
+    row i the sums before record i, the last row the totals."""
+    dtype, cols = _LIST_SCAN_KINDS[kind]
+    rec = np.ascontiguousarray(records, dtype=dtype)
+    out = np.zeros((len(rec) + 1, cols), dtype=np.uint64)
+    rc = chunker.lib.pfscdc_debug_list_scan(
+        chunker.ctx, kind, rec.ctypes.data_as(C.c_void_p), len(rec),
+        out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc:
+        msg = chunker.lib.pfscdc_last_error(chunker.ctx)
+        raise _lib.PfsCdcError(rc, msg.decode("utf-8", "replace") if msg else "")
+    return out
+
+
 class _BorrowedDevList(DevIndexList):
     """A source's list: owned by the source, which it keeps alive."""
 

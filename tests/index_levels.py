@@ -24,7 +24,7 @@ from pfs_amd import chunk as pc
 
 # index_walk_kernel stages kIdxWin + 16 bytes per pass, index_scan_kernel scans tiles of
 # kIdxScanBlock frames, index_count_kernel / index_fill_kernel / index_flags_kernel have kIdxBlock
-# lanes per workgroup (cdc_kernels.hip section 8)
+# lanes per workgroup (list_kernels.hip section 8)
 WIN = 8192 + 16
 TILE = 1024
 LANES = 256
