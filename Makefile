@@ -10,7 +10,7 @@ SRC := $(addprefix pfs_amd/csrc/,cdc_kernels.hip list_kernels.hip pfscdc.cpp wri
   index.cpp resident.cpp index_decode.cpp index_merge.cpp fileset.cpp group.cpp gorand.cpp \
   knobs.cpp glob.cpp source.cpp source_dev.cpp diff.cpp diff_dev.cpp copy_map.cpp copy_map_dev.cpp)
 HDR := include/pfscdc.h $(addprefix pfs_amd/csrc/,pfscdc_internal.h list_kernels.h index_parse.h \
-  index_list.h dev_list.h dev_pass.h source.h glob.h diff.h paths.h copy_map.h)
+  index_list.h dev_list.h dev_pass.h source.h glob.h diff.h paths.h copy_map.h tar.h)
 OBJ := $(patsubst pfs_amd/csrc/%,build/obj/%.o,$(SRC))
 
 all: pfs_amd/libpfscdc.so oracle/_build/liboracle.so

@@ -200,12 +200,29 @@ int pfscdc_last_read_timings(pfscdc_ctx* ctx, float out[2]);
  * sum(512 + roundup512(size_i)) + 1024.  The header layout is restated from archive/tar's
  * source; like everything else here it has not been held against a Go run (README "Scope and
  * correctness"), and Python's tarfile reads the stream back.
- * Not implemented: the entries Go writes PAX records for, i.e. a name that is not pure ASCII
- * 0x01-0x7F, a name longer than 100 bytes that splitUSTARPath cannot split (prefix <= 155 and
- * suffix 1-100 bytes around a '/'), a size above 077777777777 (8 GiB - 1).  Every entry point
- * below returns PFSCDC_EUNSUPPORTED for them and those with a ctx name the file in
- * pfscdc_last_error.  PFSCDC_EINVAL: an empty name, or a directory (name ending in '/') that
- * has pieces or a size. */
+ * The entries Go writes PAX records for: a name that is not pure ASCII 0x01-0x7F, a name longer
+ * than 100 bytes that splitUSTARPath cannot split (prefix <= 155 and suffix 1-100 bytes around a
+ * '/'), a size above 077777777777 (8 GiB - 1).  With the format PFSCDC_TAR_USTAR, the default,
+ * every entry point below returns PFSCDC_EUNSUPPORTED for them and those with a ctx name the
+ * file in pfscdc_last_error.  With PFSCDC_TAR_USTAR | PFSCDC_TAR_PAX such an entry, and no
+ * other, gets the head archive/tar's FormatPAX writes in front of its content: an extended
+ * header block (typeflag 'x', named dir/PaxHeaders.0/file without its non-ASCII bytes, cut at
+ * 100), the records "<n> path=<name>\n" (a name that is not ASCII or longer than 100 bytes) and
+ * "<n> size=<decimal>\n" (a size above 8 GiB - 1) padded to a multiple of 512, and the main
+ * header block with no prefix, the name without its non-ASCII bytes cut at 100, and a size field
+ * of zeros where the size does not fit: 512 + roundup512(records) + 512 bytes where a USTAR
+ * entry has 512.  An entry USTAR can hold is written as before, so a stream with no such entry
+ * is the same bytes under either format.  Restated from archive/tar's source (Go 1.16) and read
+ * back by Python's tarfile, not held against a Go run; DESIGN.md §5 lists what to confirm.
+ * Not implemented under either format (PFSCDC_EUNSUPPORTED): a PAX entry whose name has an
+ * empty, "." or ".." component (a leading '/' and a directory's trailing '/' aside), which
+ * path.Join would rewrite in the extended header's name (PFS cleans every index path, so no
+ * written commit has one), and a PAX entry's name above 65,535 bytes (the entry record's name
+ * length is 16 bits; the USTAR rules bound every other name at 256).
+ * PFSCDC_EINVAL: an empty name, or a directory (name ending in '/') that has pieces or a
+ * size. */
+#define PFSCDC_TAR_USTAR 1 /* USTAR entries only: what USTAR cannot hold is refused */
+#define PFSCDC_TAR_PAX 2   /* with PFSCDC_TAR_USTAR: such an entry is written in PAX format */
 typedef struct pfscdc_tar_file {
   const char* path;  /* index.Index.Path, NUL-terminated */
   uint32_t first;    /* its pieces are [first, first + count) of the slice / DataRef array */
@@ -221,6 +238,21 @@ int pfscdc_tar_header(const char* path, uint64_t size, uint8_t out[512]);
  * length.  Host only: what a caller sizes its buffers and windows with. */
 int pfscdc_tar_layout(const pfscdc_tar_file* files, uint32_t nfiles, const uint64_t* sizes,
                       uint64_t* entry_offsets, uint64_t* total);
+/* The head of one entry under format (PFSCDC_TAR_USTAR, or PFSCDC_TAR_USTAR | PFSCDC_TAR_PAX;
+ * anything else PFSCDC_EINVAL): every byte in front of its content, *len of them (512 for an
+ * entry USTAR can hold, then the bytes of pfscdc_tar_header), into out[0, cap) (out NULL: only
+ * *len; cap < *len: PFSCDC_EINVAL).  Host only: the specification tar_frame_kernel is tested
+ * against. */
+int pfscdc_tar_head(const char* path, uint64_t size, int format, uint8_t* out, uint64_t cap,
+                    uint64_t* len);
+/* pfscdc_tar_layout under format: an entry spans its head, its content and the padding. */
+int pfscdc_tar_layout_format(const pfscdc_tar_file* files, uint32_t nfiles, const uint64_t* sizes,
+                             int format, uint64_t* entry_offsets, uint64_t* total);
+/* The format of every later pfscdc_read_tar, pfscdc_store_read_tar, pfscdc_dev_list_tar_layout
+ * and pfscdc_dev_list_read_tar on ctx.  Not a knob: it changes the stream (for the entries named
+ * above, and for no other).  A resident list keeps the plan of the format it was last laid out
+ * under and plans again when the format has changed. */
+int pfscdc_set_tar_format(pfscdc_ctx* ctx, int format);
 /* Stream bytes [begin, min(begin + len, total)) of the files' tar stream into out (*nwritten of
  * them, nullable), over a batch of stored chunks as pfscdc_read_slices takes it: file i's
  * content is the concatenation of slices [first, first + count).  begin must be a multiple of
@@ -872,8 +904,9 @@ int pfscdc_index_merge_dev(pfscdc_ctx* ctx, int mode, const pfscdc_dev_list* con
 /* pfscdc_tar_layout for a resident list: *total the stream's length, entry_offsets (nullable,
  * count + 1 entries) as pfscdc_tar_layout's.  Runs the plan stage of pfscdc_dev_list_read_tar if
  * the handle has none yet (kernels: every DataRef's size and validity, prefix sums, per entry the
- * name rules above and the span, prefix sums of the spans) and caches it in the handle; errors as
- * pfscdc_dev_list_read_tar's name and size errors. */
+ * name rules above and the span, prefix sums of the spans) and caches it in the handle, for the
+ * ctx's tar format (pfscdc_set_tar_format: a handle planned under the other format is planned
+ * again); errors as pfscdc_dev_list_read_tar's name and size errors. */
 int pfscdc_dev_list_tar_layout(pfscdc_ctx* ctx, pfscdc_dev_list* d, uint64_t* total,
                                uint64_t* entry_offsets);
 /* pfscdc_store_read_tar over a resident list: the same window rules, the same bytes, the same

@@ -22,6 +22,7 @@ PFSCDC_ESTATE = -5
 PFSCDC_ECALLBACK = -6
 PFSCDC_ECORRUPT = -7
 PFSCDC_ENOTFOUND = -8
+TAR_USTAR, TAR_PAX = 1, 2  # PFSCDC_TAR_*: the tar format is TAR_USTAR or TAR_USTAR | TAR_PAX
 
 SEG_VALID = 1
 SEG_CUT = 2
@@ -65,7 +66,7 @@ EXPORTED = [
     "pfscdc_group_scan_stream",
     "pfscdc_read_slices", "pfscdc_last_read_timings", "pfscdc_store_read",
     "pfscdc_tar_header", "pfscdc_tar_layout", "pfscdc_read_tar", "pfscdc_last_frame_ms",
-    "pfscdc_store_read_tar",
+    "pfscdc_store_read_tar", "pfscdc_tar_head", "pfscdc_tar_layout_format", "pfscdc_set_tar_format",
     "pfscdc_uw_set_store", "pfscdc_index_list_count", "pfscdc_index_list_entries",
     "pfscdc_index_list_blob", "pfscdc_index_list_datarefs", "pfscdc_index_list_tar_files",
     "pfscdc_index_list_free", "pfscdc_index_decode_host", "pfscdc_index_filter_list",
@@ -362,6 +363,9 @@ def load() -> C.CDLL:
             "pfscdc_store_read": (i32, [vp, vp, P(FullDataRef), u32, vp, u64, i32, P(u64)]),
             "pfscdc_tar_header": (i32, [C.c_char_p, u64, vp]),
             "pfscdc_tar_layout": (i32, [P(TarFile), u32, P(u64), P(u64), P(u64)]),
+            "pfscdc_tar_head": (i32, [C.c_char_p, u64, i32, vp, u64, P(u64)]),
+            "pfscdc_tar_layout_format": (i32, [P(TarFile), u32, P(u64), i32, P(u64), P(u64)]),
+            "pfscdc_set_tar_format": (i32, [vp, i32]),
             "pfscdc_read_tar": (i32, [vp, vp, u64, i32, P(u64), u32, vp, vp, P(TarFile), u32, vp,
                                       u32, u64, u64, vp, i32, vp, P(u64)]),
             "pfscdc_last_frame_ms": (i32, [vp, P(C.c_float)]),

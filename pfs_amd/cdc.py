@@ -310,19 +310,25 @@ class Chunker:
         return {"verify": out[0], "gather": out[1]}
 
     def read_tar(self, ctext, chunk_offsets: Sequence[int], refs: np.ndarray, files, slices,
-                 begin: int = 0, length: Optional[int] = None, out=None, verified=None):
+                 begin: int = 0, length: Optional[int] = None, out=None, verified=None,
+                 pax: bool = False):
         """One window of the tar stream getFileTar writes for ``files`` (pfscdc_read_tar), over
         a batch of stored chunks as ``read_slices`` takes it.  ``files``: (path, first, count)
         triples, file i's content being slices [first, first + count); ``begin``/``length``:
         the window (multiples of 512 unless it reaches the stream's end; None = to the end);
         ``out``: optional contiguous torch uint8 tensor (CUDA or CPU) or numpy uint8 array of
-        at least the window's size.  Returns (stream bytes, chunk_ok[nchunks], nwritten)."""
+        at least the window's size.  ``pax``: this context's tar format from here on
+        (pfscdc_set_tar_format): an entry USTAR cannot hold is written in PAX format instead of
+        being refused.  Returns (stream bytes, chunk_ok[nchunks], nwritten)."""
         offs, n, refs, sl, ns, ver = self._stored_batch(chunk_offsets, refs, slices, verified)
         tf = _lib.tar_files(files)
         sizes = np.array([int(sl["size"][f:f + k].sum()) for _, f, k in files], dtype=np.uint64)
         total = C.c_uint64()
-        rc = self.lib.pfscdc_tar_layout(tf, len(files), sizes.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                        None, C.byref(total))
+        fmt = _lib.TAR_USTAR | _lib.TAR_PAX if pax else _lib.TAR_USTAR
+        self._check(self.lib.pfscdc_set_tar_format(self.ctx, fmt), "set_tar_format")
+        rc = self.lib.pfscdc_tar_layout_format(tf, len(files),
+                                               sizes.ctypes.data_as(C.POINTER(C.c_uint64)), fmt,
+                                               None, C.byref(total))
         if rc == 0:  # (else pfscdc_read_tar reports the same error with the file's name)
             window = max(0, min(total.value - begin, total.value if length is None else length))
         else:

@@ -2081,7 +2081,7 @@ __global__ void verify_ids_kernel(const pfscdc_segment* __restrict__ segs, uint3
 
 // 5f. GetFileTAR framing (api_server.go:578-593, fileset/util.go:42-53): everything of one
 // window [wbegin, wend) of the tar stream that is not file content, i.e. the 512-byte USTAR
-// headers, each entry's zero padding up to the next multiple of 512 and the trailer's two zero
+// headers (the longer heads of PAX entries: below), each entry's zero padding up to the next multiple of 512 and the trailer's two zero
 // blocks.  The content bytes are chacha_slice_gather_kernel's (its out_off is the tar layout):
 // the two kernels write disjoint bytes and every byte of the window exactly once, so the window
 // is never cleared and the launches need no order between them.  One wave per item, grid-stride
@@ -2095,7 +2095,35 @@ __global__ void verify_ids_kernel(const pfscdc_segment* __restrict__ segs, uint3
 // stores its 8 bytes with one unaligned store.  Windows begin and end on multiples of 512 (or
 // at the stream's end), so a header or trailer block is inside whole or not at all; padding is
 // clipped to the window, whole 8-byte pieces as one store and the cut piece byte by byte.
+//
+// A PAX entry (TarEntry::split <= kTarPaxPath; Go's FormatPAX, restated in pfscdc_tar_head) has
+// more blocks in front of its content: the extended header block, the record blocks, then the
+// main header block, which is the entry's own item as above.  The others are nx items of their
+// own behind the trailer's, found from the item's number by a search in xblk (the running count
+// of such blocks per entry), so a name of thousands of bytes spreads its record blocks over the
+// waves like so many entries.  Each is written whole or not at all, as a header is, so a window
+// that begins or ends inside a head gets exactly its blocks.  A record block is a function of
+// the name and the size alone: byte p of "<n> path=<name>\n<n> size=<decimal>\n" with both
+// length prefixes formed here.  The two header blocks hold the name without its bytes >= 0x80
+// (toASCII), cut at 100: the wave marks the bytes kept, 64 bytes of the name at a time, with a
+// ballot, each lane picks the kept bytes that fall into its 8 places by their rank in the mask
+// (no LDS, nothing passed between lanes but the mask), and the walk stops at the 101st byte
+// kept.  A window with no PAX entry launches the instantiation without any of this.
 constexpr int kTarBlock = 256;
+
+// byte j >= 100 of a header block outside its prefix field
+PFS_DEV uint32_t tar_fixed_byte(uint32_t j, uint64_t size, uint32_t type, bool devs) {
+  if (j < 124) return (j - 100) % 8 == 7 ? 0u : '0';  // mode, uid, gid
+  if (j < 136) return j == 135 ? 0u : '0' + (uint32_t)((size >> (3 * (134 - j))) & 7);
+  if (j < 148) return j == 147 ? 0u : '0';  // mtime
+  if (j < 156) return ' ';                  // chksum, as it is summed
+  if (j == 156) return type;
+  if (j < 257) return 0u;  // linkname
+  if (j < 265) return (uint32_t)(uint8_t)"ustar\0" "00"[j - 257];
+  if (j < 329) return 0u;  // uname, gname
+  if (j < 345) return devs && (j - 329) % 8 != 7 ? '0' : 0u;  // devmajor, devminor
+  return 0u;
+}
 
 PFS_DEV uint32_t tar_header_byte(uint32_t j, const uint8_t* __restrict__ name, uint32_t len,
                                  int32_t split, uint64_t size) {
@@ -2103,57 +2131,218 @@ PFS_DEV uint32_t tar_header_byte(uint32_t j, const uint8_t* __restrict__ name, u
     const uint32_t k = j + (uint32_t)(split + 1);
     return k < len ? name[k] : 0u;
   }
-  if (j < 124) return (j - 100) % 8 == 7 ? 0u : '0';  // mode, uid, gid
-  if (j < 136) return j == 135 ? 0u : '0' + (uint32_t)((size >> (3 * (134 - j))) & 7);
-  if (j < 148) return j == 147 ? 0u : '0';  // mtime
-  if (j < 156) return ' ';                  // chksum, as it is summed
-  if (j == 156) return name[len - 1] == '/' ? '5' : '0';
-  if (j < 257) return 0u;  // linkname
-  if (j < 265) return (uint32_t)(uint8_t)"ustar\0" "00"[j - 257];
-  if (j < 329) return 0u;  // uname, gname
-  if (j < 345) return (j - 329) % 8 == 7 ? 0u : '0';  // devmajor, devminor
-  if (j < 500) return split >= 0 && j - 345 < (uint32_t)split ? name[j - 345] : 0u;  // prefix
-  return 0u;
+  if (j >= 345 && j < 500) return split >= 0 && j - 345 < (uint32_t)split ? name[j - 345] : 0u;
+  return tar_fixed_byte(j, size, name[len - 1] == '/' ? '5' : '0', true);
 }
 
+PFS_DEV uint32_t tar_decimal_digit(uint64_t v, uint32_t k) {  // '0' + digit k from the right
+  for (; k; k--) v /= 10;
+  return '0' + (uint32_t)(v % 10);
+}
+
+// byte p of one PAX record "<n> <key>=<value>\n" of n bytes with a d-digit n; key: " path=" or
+// " size="; the value is name[0, n - d - 7) or, with name == nullptr, num in decimal
+PFS_DEV uint32_t tar_record_byte(uint32_t p, uint32_t n, uint32_t d, const char* key,
+                                 const uint8_t* __restrict__ name, uint64_t num) {
+  if (p < d) return tar_decimal_digit(n, d - 1 - p);
+  if (p < d + 6) return (uint32_t)(uint8_t)key[p - d];
+  if (p == n - 1) return '\n';
+  return name ? name[p - d - 6] : tar_decimal_digit(num, n - 2 - p);
+}
+
+PFS_DEV uint32_t tar_nth_set_bit(uint64_t m, uint32_t r) {  // index of set bit r of m (it has one)
+  uint32_t pos = 0;
+  for (uint32_t w = 32; w; w >>= 1) {
+    const uint32_t c = (uint32_t)__popcll(m & ((1ull << w) - 1));
+    if (r >= c) {
+      r -= c;
+      m >>= w;
+      pos += w;
+    }
+  }
+  return pos;
+}
+
+// byte i of v = name[0, d), then nm bytes of "PaxHeaders.0/", then name[d, len)
+PFS_DEV uint32_t tar_virtual_byte(const uint8_t* __restrict__ name, uint32_t d, uint32_t nm,
+                                  uint32_t i) {
+  return i < d ? name[i] : i < d + nm ? (uint32_t)(uint8_t)"PaxHeaders.0/"[i - d] : name[i - nm];
+}
+
+// toASCII(v), v as tar_virtual_byte's (nm == 0: the name itself): *field = this lane's bytes
+// [8 lane, 8 lane + 8) of it, zeros behind its end; returns how many bytes it has, counted up to
+// the first 64-byte step that passes 100 (the same in every lane).  The wave marks 64 bytes of v
+// at a time with a ballot; the byte at place q is the one at set bit q - (the count so far).
+PFS_DEV uint32_t tar_ascii_field(const uint8_t* __restrict__ name, uint32_t len, uint32_t d,
+                                 uint32_t nm, uint32_t lane, uint64_t* field) {
+  const uint32_t vlen = len + nm;
+  uint32_t cnt = 0;
+  uint64_t f = 0;
+  for (uint32_t base = 0; base < vlen && cnt <= 100; base += 64) {
+    const uint32_t i = base + lane;
+    const uint32_t b = i < vlen ? tar_virtual_byte(name, d, nm, i) : 0x80u;
+    const uint64_t m = __ballot(b < 0x80 && b != 0);
+    const uint32_t pc = (uint32_t)__popcll(m);
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; k++) {
+      const uint32_t q = 8 * lane + k;
+      if (q >= cnt && q - cnt < pc)
+        f |= (uint64_t)tar_virtual_byte(name, d, nm, base + tar_nth_set_bit(m, q - cnt)) << (8 * k);
+    }
+    cnt += pc;
+  }
+  *field = f;
+  return cnt;
+}
+
+// the length of the field's first lim (<= 100) bytes without their trailing '/' (in every lane)
+PFS_DEV uint32_t tar_trimmed_len(uint64_t field, uint32_t lim, uint32_t lane) {
+  uint32_t t = 0;
+  for (uint32_t k = 0; k < 8; k++)
+    if (8 * lane + k < lim && ((field >> (8 * k)) & 0xff) != '/') t = 8 * lane + k + 1;
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t u = (uint32_t)__shfl_xor((int)t, o, 64);
+    t = t > u ? t : u;
+  }
+  return t;
+}
+
+// the checksum into bytes 148-155 of the block whose lanes hold v (byte sums: sum), then the store
+PFS_DEV void tar_store_header(uint64_t v, uint32_t sum, uint32_t lane, uint8_t* at) {
+  for (int o = 32; o > 0; o >>= 1) sum += (uint32_t)__shfl_xor((int)sum, o, 64);
+  // 6 octal digits, NUL, space: bytes 148-151 are lane 18's upper half, 152-155 lane 19's
+  // lower half
+  if (lane == 18)
+    v = (v & 0xffffffffull) | (uint64_t)('0' + ((sum >> 15) & 7)) << 32 |
+        (uint64_t)('0' + ((sum >> 12) & 7)) << 40 | (uint64_t)('0' + ((sum >> 9) & 7)) << 48 |
+        (uint64_t)('0' + ((sum >> 6) & 7)) << 56;
+  if (lane == 19)
+    v = (v & ~0xffffffffull) | (uint64_t)('0' + ((sum >> 3) & 7)) |
+        (uint64_t)('0' + (sum & 7)) << 8 | (uint64_t)' ' << 24;
+  __builtin_memcpy(at + 8 * lane, &v, 8);
+}
+
+// One of the nx blocks of PAX entries in front of their main headers: block j of en's head, the
+// extended header block (j == 0) or record block j - 1.
+PFS_DEV void tar_pax_block(const TarEntry& en, uint32_t j, const uint8_t* __restrict__ name,
+                           uint32_t lane, uint8_t* at) {
+  const uint32_t len = en.name_len;
+  const bool has_path = en.split == kTarPaxPath, has_size = en.size > kTarMaxSize;
+  const uint32_t n1 = has_path ? tar_pax_record_len(4, len) : 0;
+  const uint32_t n2 = has_size ? tar_pax_record_len(4, tar_digits(en.size)) : 0;
+  uint64_t v = 0;
+  if (j) {
+    const uint32_t d1 = tar_digits(n1), d2 = tar_digits(n2);
+#pragma unroll 1
+    for (uint32_t k = 0; k < 8; k++) {
+      const uint32_t p = 512 * (j - 1) + 8 * lane + k;
+      uint32_t b = 0;
+      if (p < n1) b = tar_record_byte(p, n1, d1, " path=", name, 0);
+      else if (p < n1 + n2) b = tar_record_byte(p - n1, n2, d2, " size=", nullptr, en.size);
+      v |= (uint64_t)b << (8 * k);
+    }
+    __builtin_memcpy(at + 8 * lane, &v, 8);
+    return;
+  }
+  // dir + "PaxHeaders.0" [+ "/" + file], dir ending behind the name's last '/'
+  uint32_t d = 0;
+  for (uint32_t hi = len; hi > 0 && d == 0;) {
+    const uint32_t lo = hi > 64 ? hi - 64 : 0, i = lo + lane;
+    const uint64_t m = __ballot(i < hi && name[i] == '/');
+    if (m) d = lo + 64 - (uint32_t)__clzll(m);
+    hi = lo;
+  }
+  uint64_t field;
+  const uint32_t cnt = tar_ascii_field(name, len, d, d < len ? 13 : 12, lane, &field);
+  const uint32_t m = tar_trimmed_len(field, cnt < 100 ? cnt : 100, lane);
+  uint32_t sum = 0;
+#pragma unroll 1
+  for (uint32_t k = 0; k < 8; k++) {
+    const uint32_t q = 8 * lane + k;
+    const uint32_t b = q < 100 ? (q < m ? (uint32_t)(field >> (8 * k)) & 0xff : 0u)
+                               : tar_fixed_byte(q, n1 + n2, 'x', false);
+    v |= (uint64_t)b << (8 * k);
+    sum += b;
+  }
+  tar_store_header(v, sum, lane, at);
+}
+
+// a PAX entry's main header block: no prefix, toASCII(name) cut at 100, zeros for a size that
+// does not fit
+PFS_DEV void tar_pax_main(const TarEntry& en, const uint8_t* __restrict__ name, uint32_t lane,
+                          uint8_t* at) {
+  uint64_t field;
+  const uint32_t cnt = tar_ascii_field(name, en.name_len, 0, 0, lane, &field);
+  const uint32_t m = cnt < 100 ? cnt : 100;
+  // formatString: a cut that ends in '/' (trimmed < 100) loses the first of its last '/'
+  const uint32_t trimmed = tar_trimmed_len(field, m, lane);
+  const uint32_t cut = cnt > 100 ? trimmed : 100;
+  const uint64_t size = en.size > kTarMaxSize ? 0 : en.size;
+  const uint32_t type = name[en.name_len - 1] == '/' ? '5' : '0';
+  uint64_t v = 0;
+  uint32_t sum = 0;
+#pragma unroll 1
+  for (uint32_t k = 0; k < 8; k++) {
+    const uint32_t q = 8 * lane + k;
+    const uint32_t b = q < 100 ? (q < m && q != cut ? (uint32_t)(field >> (8 * k)) & 0xff : 0u)
+                               : tar_fixed_byte(q, size, type, true);
+    v |= (uint64_t)b << (8 * k);
+    sum += b;
+  }
+  tar_store_header(v, sum, lane, at);
+}
+
+// kPax == false: the launch for a window with no PAX entry (nx == 0), which is the USTAR kernel
+// as it was: no head length to work out, no items behind the trailer's, 26 VGPRs against 44.
+template <bool kPax>
 __global__ __launch_bounds__(kTarBlock) void tar_frame_kernel(
     const TarEntry* __restrict__ entries, const uint8_t* __restrict__ names, uint32_t n,
-    uint64_t wbegin, uint64_t wend, uint64_t total, uint8_t* __restrict__ out) {
+    const uint64_t* __restrict__ xblk, uint64_t nx, uint64_t wbegin, uint64_t wend, uint64_t total,
+    uint8_t* __restrict__ out) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint64_t nwaves = (uint64_t)gridDim.x * (kTarBlock / 64);
-  for (uint64_t e = (uint64_t)blockIdx.x * (kTarBlock / 64) + wv; e < (uint64_t)n + 2;
-       e += nwaves) {
+  for (uint64_t e = (uint64_t)blockIdx.x * (kTarBlock / 64) + wv;
+       e < (uint64_t)n + 2 + (kPax ? nx : 0); e += nwaves) {
     uint64_t z0, z1;  // the item's zero bytes, as stream offsets
-    if (e >= n) {     // a trailer block
+    if (kPax && e >= (uint64_t)n + 2) {  // block j of the head of the entry i with xblk[i] <= x < xblk[i + 1]
+      const uint64_t x = xblk[0] + (e - n - 2);
+      uint32_t i = 0;
+      for (uint32_t hi = n; hi - i > 1;) {
+        const uint32_t mid = i + (hi - i) / 2;
+        if (xblk[mid] <= x) i = mid;
+        else hi = mid;
+      }
+      const TarEntry en = entries[i];
+      const uint64_t j = x - xblk[i], at = en.off + 512 * j;
+      if (en.split <= kTarPaxPath && at >= wbegin && at < wend)
+        tar_pax_block(en, (uint32_t)j, names + en.name_off, lane, out + (at - wbegin));
+      continue;
+    }
+    if (e >= n) {  // a trailer block
       z0 = total - 1024 + 512 * (e - n);
       z1 = z0 + 512;
     } else {
       const TarEntry en = entries[e];
-      if (en.off >= wbegin && en.off < wend) {
+      const uint64_t head = en.off + (kPax ? tar_head_len(en.name_len, en.size, en.split) : 512);
+      if (head - 512 >= wbegin && head - 512 < wend) {
         const uint8_t* name = names + en.name_off;
-        uint64_t v = 0;
-        uint32_t sum = 0;
+        if (kPax && en.split <= kTarPaxPath) {
+          tar_pax_main(en, name, lane, out + (head - 512 - wbegin));
+        } else {
+          uint64_t v = 0;
+          uint32_t sum = 0;
 #pragma unroll 1  // (8 copies of the case analysis spill SGPRs: 83 VGPRs against 22)
-        for (uint32_t k = 0; k < 8; k++) {
-          const uint32_t b = tar_header_byte(8 * lane + k, name, en.name_len, en.split, en.size);
-          v |= (uint64_t)b << (8 * k);
-          sum += b;
+          for (uint32_t k = 0; k < 8; k++) {
+            const uint32_t b = tar_header_byte(8 * lane + k, name, en.name_len, en.split, en.size);
+            v |= (uint64_t)b << (8 * k);
+            sum += b;
+          }
+          tar_store_header(v, sum, lane, out + (head - 512 - wbegin));
         }
-        for (int o = 32; o > 0; o >>= 1) sum += (uint32_t)__shfl_xor((int)sum, o, 64);
-        // 6 octal digits, NUL, space: bytes 148-151 are lane 18's upper half, 152-155 lane 19's
-        // lower half
-        if (lane == 18)
-          v = (v & 0xffffffffull) | (uint64_t)('0' + ((sum >> 15) & 7)) << 32 |
-              (uint64_t)('0' + ((sum >> 12) & 7)) << 40 | (uint64_t)('0' + ((sum >> 9) & 7)) << 48 |
-              (uint64_t)('0' + ((sum >> 6) & 7)) << 56;
-        if (lane == 19)
-          v = (v & ~0xffffffffull) | (uint64_t)('0' + ((sum >> 3) & 7)) |
-              (uint64_t)('0' + (sum & 7)) << 8 | (uint64_t)' ' << 24;
-        __builtin_memcpy(out + (en.off - wbegin) + 8 * lane, &v, 8);
       }
-      z0 = en.off + 512 + en.size;
-      z1 = en.off + 512 + ((en.size + 511) & ~511ull);
+      z0 = head + en.size;
+      z1 = head + ((en.size + 511) & ~511ull);
     }
     z0 = z0 > wbegin ? z0 : wbegin;
     z1 = z1 < wend ? z1 : wend;
@@ -2494,17 +2683,24 @@ hipError_t launch_slice_gather(const uint8_t* ctext, const uint64_t* chunk_offs,
   return hipGetLastError();
 }
 
-// Launch width of tar_frame_kernel: workgroups = min(ceil((n + 2) / 4), 8 * num_cus), capped by
-// the PFSCDC_CHACHA_GRID knob; 4 waves each, one item (entry or trailer block) per wave and
-// pass.  8 workgroups of 4 waves fill a CU's 32 wave slots.
+// Launch width of tar_frame_kernel: workgroups = min(ceil((n + 2 + nx) / 4), 8 * num_cus), capped
+// by the PFSCDC_CHACHA_GRID knob; 4 waves each, one item (entry, trailer block, or one of the nx
+// other head blocks of PAX entries) per wave and pass.  8 workgroups of 4 waves fill a CU's 32
+// wave slots.
 hipError_t launch_tar_frame(const TarEntry* d_entries, const uint8_t* d_names, uint32_t n,
-                            uint64_t begin, uint64_t end, uint64_t total, uint8_t* out,
-                            int num_cus, hipStream_t st) {
+                            const uint64_t* d_xblk, uint64_t nx, uint64_t begin, uint64_t end,
+                            uint64_t total, uint8_t* out, int num_cus, hipStream_t st) {
   if (end <= begin) return hipSuccess;
-  const uint64_t per = kTarBlock / 64, need = ((uint64_t)n + 2 + per - 1) / per,
+  if (!d_xblk) nx = 0;
+  const uint64_t per = kTarBlock / 64, need = ((uint64_t)n + 2 + nx + per - 1) / per,
                  full = (uint64_t)num_cus * 8;
-  tar_frame_kernel<<<capped_grid(need < full ? need : full, Knob::ChachaGrid), kTarBlock, 0,
-                     st>>>(d_entries, d_names, n, begin, end, total, out);
+  const unsigned grid = capped_grid(need < full ? need : full, Knob::ChachaGrid);
+  if (nx)  // (every PAX entry has at least two such blocks: nx == 0 is a window without one)
+    tar_frame_kernel<true><<<grid, kTarBlock, 0, st>>>(d_entries, d_names, n, d_xblk, nx, begin,
+                                                       end, total, out);
+  else
+    tar_frame_kernel<false><<<grid, kTarBlock, 0, st>>>(d_entries, d_names, n, nullptr, 0, begin,
+                                                        end, total, out);
   return hipGetLastError();
 }
 

@@ -11,12 +11,15 @@ struct pfscdc_dev_list {
   int device = 0;
   void *entries = nullptr, *blob = nullptr, *drs = nullptr;  // hipMalloc'ed, owned
   uint64_t n = 0, nr = 0, nb = 0;                            // entries, DataRefs, blob bytes
-  // the plan stage of pfscdc_dev_list_read_tar, made once
+  // the plan stage of pfscdc_dev_list_read_tar, made once per tar format (plan_format: the one
+  // it holds)
   bool planned = false;
+  int plan_format = 0;
   int plan_rc = 0;
   std::string plan_err;
   uint64_t total = 0;
   void *dpre = nullptr, *ent = nullptr, *off = nullptr;  // nr + 1 sums, n TarEntry, n + 1 offsets
+  void* xblk = nullptr;  // n + 1 running counts of PAX head blocks; nullptr where there is none
   ~pfscdc_dev_list();
 };
 

@@ -100,6 +100,8 @@ enum RtarWhy : uint32_t {
   kRtarNotAscii,
   kRtarTooBig,
   kRtarNoSplit,
+  kRtarPaxLong,   // with PFSCDC_TAR_PAX: a PAX name above kTarMaxName bytes
+  kRtarPaxJoin,   // ... or one path.Join would rewrite (tar_name_joins)
   kRtarDirPieces,
 };
 constexpr unsigned long long kRtarNoErr = ~0ull;  // else entry index << 8 | RtarWhy
@@ -115,14 +117,18 @@ hipError_t launch_rtar_sizes(const pfscdc_full_dataref* drs, uint64_t nr, uint64
 // out[0, n] = saturating exclusive prefix sums of in[0, n); ent (nullable): ent[i].off = out[i]
 hipError_t launch_rtar_scan(const uint64_t* in, uint64_t n, uint64_t* out, TarEntry* ent,
                             hipStream_t st);
-// per entry: the checks of tar_plan, ent[i] (off unset) and span[i] = 512 + roundup512(size)
-// (0 for a refused entry); *err = min(entry << 8 | RtarWhy) (preset to kRtarNoErr)
-hipError_t launch_rtar_entries(const RtarList& l, const uint64_t* dpre, TarEntry* ent,
-                               uint64_t* span, unsigned long long* err, int num_cus,
+// per entry: the checks of tar_plan under format, ent[i] (off unset), span[i] = head +
+// roundup512(size) (0 for a refused entry) and, where xb is not nullptr, xb[i] = head / 512 - 1;
+// *err = min(entry << 8 | RtarWhy) (preset to kRtarNoErr)
+hipError_t launch_rtar_entries(const RtarList& l, const uint64_t* dpre, int format, TarEntry* ent,
+                               uint64_t* span, uint64_t* xb, unsigned long long* err, int num_cus,
                                hipStream_t st);
-// the entries that meet stream bytes [begin, end), by searches in off[0, n]
-hipError_t launch_rtar_window(const RtarList& l, const uint64_t* off, uint64_t begin, uint64_t end,
-                              RtarWindow* w, hipStream_t st);
+// the entries that meet stream bytes [begin, end), by searches in off[0, n]; xblk (nullable): the
+// prefix sums of launch_rtar_entries' xb, and then *nx = xblk[w->i1] - xblk[w->i0], the head
+// blocks of those entries other than main headers
+hipError_t launch_rtar_window(const RtarList& l, const uint64_t* off, const uint64_t* xblk,
+                              uint64_t begin, uint64_t end, RtarWindow* w, uint64_t* nx,
+                              hipStream_t st);
 // Pieces of DataRefs [w.k0, w.k1) clipped to the window.  Count pass (slices == nullptr):
 // cnt[k - k0] = {non-empty, run head, keystream blocks}.  Fill pass, after launch_merge_scan of
 // cnt into base: the dense slices (chunk = the run's number), out_off, blk_base (m + 1) and runs.

@@ -537,13 +537,16 @@ hipError_t launch_list_copy(const pfscdc_full_dataref* src, const MrgCopy* copy,
 //               tar_name_check over the path in the blob; the TarEntry record (name_off =
 //               path_off: the blob is the name table) and the span.  The lowest refused entry
 //               and its reason leave through one atomic minimum.
-//  10b again    offsets = prefix sums of the spans, written into the TarEntry records as well.
+//  10b again    offsets = prefix sums of the spans, written into the TarEntry records as well;
+//               with PAX allowed (pfscdc_set_tar_format) once more over the entries' head blocks
+//               other than the main header: xblk, what tar_frame_kernel finds such a block by.
 // Window, per call:
 //  10d window   one lane: the entries [i0, i1) that meet [begin, end) by two searches in the
 //               offsets, and their DataRefs [k0, k1).
 //  10e pieces   one lane per DataRef of [k0, k1) (a 300-DataRef file is 300 lanes, not a loop):
 //               its file by a search in the entries' first (the last entry with first <= k, which
-//               skips entries of count 0), its place p = off + 512 + dpre[k] - dpre[first], the
+//               skips entries of count 0), its place p = off + head + dpre[k] - dpre[first]
+//               (head: tar_head_len, 512 for a USTAR entry), the
 //               clip to the window as TarPiece.  A non-empty piece is a run head when the DataRef
 //               before it gave no piece or names another chunk or another size of it.  Count pass, merge_scan_kernel
 //               over {piece, head, keystream blocks}, fill pass: the dense arrays
@@ -626,8 +629,8 @@ __global__ __launch_bounds__(kIdxScanBlock) void rtar_scan_kernel(
 }
 
 __global__ __launch_bounds__(kIdxBlock) void rtar_entries_kernel(
-    RtarList l, const uint64_t* __restrict__ dpre, TarEntry* __restrict__ ent,
-    uint64_t* __restrict__ span, unsigned long long* __restrict__ err) {
+    RtarList l, const uint64_t* __restrict__ dpre, int format, TarEntry* __restrict__ ent,
+    uint64_t* __restrict__ span, uint64_t* __restrict__ xb, unsigned long long* __restrict__ err) {
   for (uint64_t i = (uint64_t)blockIdx.x * kIdxBlock + threadIdx.x; i < l.n;
        i += (uint64_t)gridDim.x * kIdxBlock) {
     const pfscdc_index_entry e = l.entries[i];
@@ -669,17 +672,31 @@ __global__ __launch_bounds__(kIdxBlock) void rtar_entries_kernel(
           if (k < 2 || len - k > 100 || len - k == 0 || k - 1 > 155) why = kRtarNoSplit;
           else split = (int32_t)(k - 1);
         }
+        if (why && (format & PFSCDC_TAR_PAX)) {  // tar_name_check's PAX arm
+          if (len > kTarMaxName) {
+            why = kRtarPaxLong;
+          } else if (!tar_name_joins(name, (uint32_t)len)) {
+            why = kRtarPaxJoin;
+          } else {
+            split = why == kRtarNotAscii || len > 100 ? kTarPaxPath : kTarPaxSize;
+            why = 0;
+          }
+        }
         if (!why && name[len - 1] == '/' && count) why = kRtarDirPieces;
       }
     }
     if (why) atomicMin(err, (unsigned long long)(i << 8 | why));
     ent[i] = TarEntry{0, z, (uint32_t)e.path_off, (uint16_t)len, (int16_t)split};
-    span[i] = why ? 0 : 512 + ((z + 511) & ~511ull);
+    const uint64_t head = tar_head_len((uint32_t)(len & 0xffff), z, split);
+    span[i] = why ? 0 : head + ((z + 511) & ~511ull);
+    if (xb) xb[i] = why ? 0 : head / 512 - 1;
   }
 }
 
-__global__ void rtar_window_kernel(RtarList l, const uint64_t* __restrict__ off, uint64_t begin,
-                                   uint64_t end, RtarWindow* __restrict__ w) {
+__global__ void rtar_window_kernel(RtarList l, const uint64_t* __restrict__ off,
+                                   const uint64_t* __restrict__ xblk, uint64_t begin,
+                                   uint64_t end, RtarWindow* __restrict__ w,
+                                   uint64_t* __restrict__ nx) {
   if (blockIdx.x || threadIdx.x) return;
   uint64_t lo = 0, hi = l.n + 1;  // the first i of off[0, n] with off[i] > begin
   while (lo < hi) {
@@ -696,6 +713,7 @@ __global__ void rtar_window_kernel(RtarList l, const uint64_t* __restrict__ off,
     else lo = mid + 1;
   }
   RtarWindow r{i0 < l.n ? i0 : l.n, lo, 0, 0};
+  if (xblk) *nx = r.i0 < r.i1 ? xblk[r.i1] - xblk[r.i0] : 0;
   if (r.i0 < r.i1) {
     r.k0 = l.entries[r.i0].first;
     r.k1 = (uint64_t)l.entries[r.i1 - 1].first + l.entries[r.i1 - 1].count;
@@ -714,7 +732,9 @@ PFS_DEV RtarClip rtar_clip(const RtarPieces& p, uint64_t k) {
     if (p.l.entries[mid].first <= k) lo = mid;
     else hi = mid;
   }
-  const uint64_t at = p.ent[lo].off + 512 + (p.dpre[k] - p.dpre[p.l.entries[lo].first]);
+  const TarEntry en = p.ent[lo];
+  const uint64_t at = en.off + tar_head_len(en.name_len, en.size, en.split) +
+                      (p.dpre[k] - p.dpre[p.l.entries[lo].first]);
   const uint64_t sz = p.dpre[k + 1] - p.dpre[k];
   const uint64_t a = at > p.begin ? at : p.begin, b = at + sz < p.end ? at + sz : p.end;
   if (a >= b) return RtarClip{0, 0, 0};
@@ -805,17 +825,19 @@ hipError_t launch_rtar_scan(const uint64_t* in, uint64_t n, uint64_t* out, TarEn
   return hipGetLastError();
 }
 
-hipError_t launch_rtar_entries(const RtarList& l, const uint64_t* dpre, TarEntry* ent,
-                               uint64_t* span, unsigned long long* err, int num_cus,
+hipError_t launch_rtar_entries(const RtarList& l, const uint64_t* dpre, int format, TarEntry* ent,
+                               uint64_t* span, uint64_t* xb, unsigned long long* err, int num_cus,
                                hipStream_t st) {
   if (l.n == 0) return hipSuccess;
-  rtar_entries_kernel<<<merge_grid(l.n, num_cus), kIdxBlock, 0, st>>>(l, dpre, ent, span, err);
+  rtar_entries_kernel<<<merge_grid(l.n, num_cus), kIdxBlock, 0, st>>>(l, dpre, format, ent, span,
+                                                                       xb, err);
   return hipGetLastError();
 }
 
-hipError_t launch_rtar_window(const RtarList& l, const uint64_t* off, uint64_t begin, uint64_t end,
-                              RtarWindow* w, hipStream_t st) {
-  rtar_window_kernel<<<1, 64, 0, st>>>(l, off, begin, end, w);
+hipError_t launch_rtar_window(const RtarList& l, const uint64_t* off, const uint64_t* xblk,
+                              uint64_t begin, uint64_t end, RtarWindow* w, uint64_t* nx,
+                              hipStream_t st) {
+  rtar_window_kernel<<<1, 64, 0, st>>>(l, off, xblk, begin, end, w, nx);
   return hipGetLastError();
 }
 
@@ -911,16 +933,7 @@ PFS_DEV bool src_entry_ok(const RtarList& in, const pfscdc_index_entry& e) {
 // IsClean(p, false) for s[0, n): rooted, no empty component, none of "." or ".."; with
 // allow_trailing_slash IsClean(p, IsDir(p)): the last component may be empty
 PFS_DEV bool path_is_clean(const uint8_t* s, uint32_t n, bool allow_trailing_slash) {
-  bool clean = n > 0 && s[0] == '/';
-  for (uint32_t k = 1, start = 1; clean && k <= n; k++) {
-    if (k < n && s[k] != '/') continue;
-    const uint32_t cl = k - start;
-    if (cl == 0) clean = allow_trailing_slash && k == n;
-    else if (cl == 1) clean = s[start] != '.';
-    else if (cl == 2) clean = s[start] != '.' || s[start + 1] != '.';
-    start = k + 1;
-  }
-  return clean;
+  return n > 0 && s[0] == '/' && path_components_clean(s, n, 1, allow_trailing_slash);
 }
 
 // Entry i > 0 (e, inside the arrays) against the entry before it.  false and kSrcMalformed in

@@ -132,6 +132,9 @@ struct pfscdc_ctx {
   DevBuf<uint8_t> d_tnames;
   PinnedBuf<TarEntry> h_tar;
   PinnedBuf<uint8_t> h_tnames;
+  DevBuf<uint64_t> d_txblk;  // TarPlan::xblk, where the window has a PAX entry
+  PinnedBuf<uint64_t> h_txblk;
+  int tar_format = PFSCDC_TAR_USTAR;  // pfscdc_set_tar_format
   // before the verification, the gather, after it, after the tar framing
   hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};
   float read_ms[2] = {0.f, 0.f};
@@ -186,6 +189,7 @@ PassStats& ctx_source_stats(pfscdc_ctx* ctx) { return ctx->source_stats; }
 PassStats& ctx_diff_stats(pfscdc_ctx* ctx) { return ctx->diff_stats; }
 PassStats& ctx_copy_map_stats(pfscdc_ctx* ctx) { return ctx->copy_map_stats; }
 int ctx_num_cus(const pfscdc_ctx* ctx) { return ctx->num_cus; }
+int ctx_tar_format(const pfscdc_ctx* ctx) { return ctx->tar_format; }
 }  // namespace pfscdc
 
 namespace {
@@ -520,6 +524,8 @@ int pfscdc_ctx_destroy(pfscdc_ctx* c) {
   c->d_tnames.release();
   c->h_tar.release();
   c->h_tnames.release();
+  c->d_txblk.release();
+  c->h_txblk.release();
   for (auto& e : c->rev)
     if (e) (void)hipEventDestroy(e);
   if (c->d_table) (void)hipFree(c->d_table);
@@ -1456,6 +1462,14 @@ int pfscdc_last_frame_ms(pfscdc_ctx* c, float* ms) {
   return PFSCDC_OK;
 }
 
+int pfscdc_set_tar_format(pfscdc_ctx* c, int format) {
+  if (!c) return PFSCDC_EINVAL;
+  if (format != PFSCDC_TAR_USTAR && format != (PFSCDC_TAR_USTAR | PFSCDC_TAR_PAX))
+    return fail(c, PFSCDC_EINVAL, "unknown tar format");
+  c->tar_format = format;
+  return PFSCDC_OK;
+}
+
 int pfscdc_read_tar(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctext_on_device,
                     const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
                     const uint8_t* verified, const pfscdc_tar_file* files, uint32_t nfiles,
@@ -1477,7 +1491,7 @@ int pfscdc_read_tar(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctext
     sizes[i] = s.size;
   }
   TarPlan plan;
-  int rc = tar_plan(files, nfiles, sizes.data(), nslices, begin, len, &plan);
+  int rc = tar_plan(files, nfiles, sizes.data(), nslices, begin, len, c->tar_format, &plan);
   if (rc) return fail(c, rc, plan.err);
   std::vector<pfscdc_slice> clipped(plan.pieces.size());
   for (size_t k = 0; k < clipped.size(); k++) {
@@ -1638,6 +1652,8 @@ struct ReadRun {
   const uint8_t* d_names;
   uint32_t nent;
   uint64_t begin, end, total;
+  const uint64_t* d_xblk;
+  uint64_t nx;
   uint8_t* chunk_ok;
 };
 
@@ -1651,7 +1667,8 @@ static ReadRun read_run(const uint8_t* in, uint64_t nbytes, uint32_t nchunks, co
   return ReadRun{in, nbytes, nchunks, (uint32_t)b.n, b.longest, b.sum, strict, named,  //
                  sl.slices, sl.out_off, sl.blk_base, sl.m, sl.nblocks,                 //
                  outp, out, out_on_device, out_bytes,                                  //
-                 tar != nullptr, t.entries, t.names, t.nent, t.begin, t.end, t.total, chunk_ok};
+                 tar != nullptr, t.entries, t.names, t.nent, t.begin, t.end, t.total, t.xblk, t.nx,
+                 chunk_ok};
 }
 
 static int read_slices_run(pfscdc_ctx* c, const ReadRun& r) {
@@ -1677,8 +1694,8 @@ static int read_slices_run(pfscdc_ctx* c, const ReadRun& r) {
                                  r.d_out_off, r.d_blk, r.m, r.nblocks, r.outp, c->num_cus, st));
   PFS_HIP(c, hipEventRecord(c->rev[2], st));
   if (r.tar) {
-    PFS_HIP(c, launch_tar_frame(r.d_tar, r.d_names, r.nent, r.begin, r.end, r.total, r.outp,
-                                c->num_cus, st));
+    PFS_HIP(c, launch_tar_frame(r.d_tar, r.d_names, r.nent, r.d_xblk, r.nx, r.begin, r.end,
+                                r.total, r.outp, c->num_cus, st));
     PFS_HIP(c, hipEventRecord(c->rev[3], st));
   }
   if (!r.out_on_device && r.out_bytes)
@@ -1801,6 +1818,14 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
     PFS_HIP(c, hipMemcpyAsync(c->d_tnames.p, c->h_tnames.p, tar->names.size(),
                               hipMemcpyHostToDevice, st));
   }
+  const bool pax = tar && !tar->xblk.empty();  // (nent + 1 counts, the last one > 0)
+  if (pax) {
+    PFS_HIP(c, c->h_txblk.ensure(nent + 1));
+    PFS_HIP(c, c->d_txblk.ensure(nent + 1));
+    std::memcpy(c->h_txblk.p, tar->xblk.data(), sizeof(uint64_t) * (nent + 1));
+    PFS_HIP(c, hipMemcpyAsync(c->d_txblk.p, c->h_txblk.p, sizeof(uint64_t) * (nent + 1),
+                              hipMemcpyHostToDevice, st));
+  }
   PFS_HIP(c, b.upload_offsets(st));
   if (nchunks) {
     PFS_HIP(c, hipMemcpyAsync(c->d_refs.p, c->h_refs.p, sizeof(pfscdc_ref) * nchunks,
@@ -1816,7 +1841,9 @@ int read_slices_impl(pfscdc_ctx* c, const void* ctext, uint64_t nbytes, int ctex
                             hipMemcpyHostToDevice, st));
   const DevSlices sl{c->d_rslices.p, c->d_rmeta.p, c->d_rmeta.p + m + 1, m, nblocks};
   DevTar frame{};
-  if (tar) frame = DevTar{c->d_tar.p, c->d_tnames.p, nent, tar->begin, tar->end, tar->total};
+  if (tar)
+    frame = DevTar{c->d_tar.p,  c->d_tnames.p, nent, tar->begin, tar->end, tar->total,
+                   pax ? c->d_txblk.p : nullptr, pax ? tar->xblk.back() : 0};
   const ReadRun run = read_run(in, nbytes, nchunks, b, strict, named.data(), sl,
                                tar ? &frame : nullptr, outp, out, out_on_device, out_bytes,
                                chunk_ok);

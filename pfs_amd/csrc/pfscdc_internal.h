@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/pfscdc.h"
+#include "tar.h"
 
 namespace pfscdc {
 
@@ -221,46 +222,12 @@ hipError_t launch_slice_gather(const uint8_t* ctext, const uint64_t* chunk_offs,
                                const pfscdc_slice* slices, const uint64_t* out_off,
                                const uint64_t* blk_base, uint32_t n, uint64_t nblocks,
                                uint8_t* out, int num_cus, hipStream_t st);
-// One tar entry as tar_frame_kernel takes it: where its header lies in the stream, the size
-// field, and its name in the packed name table (split: index of the '/' that splitUSTARPath
-// cuts at, -1 for none).
-struct TarEntry {
-  uint64_t off;   // stream offset of the 512-byte header
-  uint64_t size;  // content bytes (the padding follows them up to the next multiple of 512)
-  uint32_t name_off;
-  uint16_t name_len;
-  int16_t split;
-};
-static_assert(sizeof(TarEntry) == 24, "tar entry record layout");
-constexpr uint64_t kTarMaxSize = 077777777777ull;  // 11 octal digits: above it Go writes PAX
-// Why a name or size has no USTAR header (nullptr: it has one); *split as TarEntry::split.
-// *rc: PFSCDC_EUNSUPPORTED where Go would write PAX records, PFSCDC_EINVAL for an empty name or
-// a directory (name ending in '/') with content.
-const char* tar_name_check(const char* name, size_t len, uint64_t size, int* split, int* rc);
-// One window [begin, end) of the stream of getFileTar over files whose pieces are
-// [first, first + count) of an array of npieces pieces (slices or DataRefs) of piece_sizes
-// bytes: the entries that meet the window, their names, and the pieces' bytes inside it.
-struct TarPiece {
-  uint32_t src;      // index of the piece in the caller's array
-  uint64_t skip;     // bytes of the piece in front of the window
-  uint64_t size;     // bytes of it inside the window (> 0)
-  uint64_t out_off;  // where they go, relative to begin
-};
-struct TarPlan {
-  uint64_t total = 0, begin = 0, end = 0;
-  std::vector<TarEntry> entries;
-  std::string names;
-  std::vector<TarPiece> pieces;
-  std::string err;
-};
-// PFSCDC_EINVAL / PFSCDC_EUNSUPPORTED with plan->err set; no GPU call
-int tar_plan(const pfscdc_tar_file* files, uint32_t nfiles, const uint64_t* piece_sizes,
-             uint32_t npieces, uint64_t begin, uint64_t len, TarPlan* plan);
-// headers, padding and trailer of plan's window into out (stream byte plan.begin = out[0]);
-// d_entries / d_names: the plan's entries and names on the device
+// heads, padding and trailer of plan's window into out (stream byte plan.begin = out[0]);
+// d_entries / d_names: the plan's entries and names on the device; d_xblk (nullptr where
+// nx == 0): the n + 1 running counts of TarPlan::xblk, from any base, nx = d_xblk[n] - d_xblk[0]
 hipError_t launch_tar_frame(const TarEntry* d_entries, const uint8_t* d_names, uint32_t n,
-                            uint64_t begin, uint64_t end, uint64_t total, uint8_t* out,
-                            int num_cus, hipStream_t st);
+                            const uint64_t* d_xblk, uint64_t nx, uint64_t begin, uint64_t end,
+                            uint64_t total, uint8_t* out, int num_cus, hipStream_t st);
 int ctx_fail(pfscdc_ctx* ctx, int code, const std::string& msg);  // sets pfscdc_last_error
 // a failed HIP call fails the ctx's call: PFSCDC_ENOMEM or PFSCDC_EHIP, the expression in the text
 #define PFS_HIP(ctx, expr)                                                             \
@@ -298,6 +265,8 @@ struct DevTar {
   const uint8_t* names;
   uint32_t nent;
   uint64_t begin, end, total;
+  const uint64_t* xblk;  // as launch_tar_frame's d_xblk
+  uint64_t nx;
 };
 int read_slices_dev_impl(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes,
                          const uint64_t* chunk_offsets, uint32_t nchunks, const pfscdc_ref* refs,
@@ -308,6 +277,7 @@ int read_slices_dev_impl(pfscdc_ctx* ctx, const void* ctext, uint64_t nbytes,
 hipError_t launch_rebase_files(pfscdc_segment* segs, uint64_t n, uint32_t base, hipStream_t st);
 // ---- what the ctx and the store hold for the index list passes (list_kernels.h) ----
 int ctx_num_cus(const pfscdc_ctx* ctx);
+int ctx_tar_format(const pfscdc_ctx* ctx);  // pfscdc_set_tar_format
 // what pfscdc_last_index_stats / pfscdc_last_index_timings report
 struct IndexStats {
   uint64_t n[4] = {};

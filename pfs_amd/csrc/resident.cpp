@@ -11,7 +11,7 @@
 #include "dev_pass.h"
 
 pfscdc_dev_list::~pfscdc_dev_list() {
-  for (void* p : {entries, blob, drs, dpre, ent, off})
+  for (void* p : {entries, blob, drs, dpre, ent, off, xblk})
     if (p) (void)hipFree(p);
 }
 
@@ -47,10 +47,20 @@ int fetch_path(pfscdc_ctx* ctx, const pfscdc_dev_list& d, uint64_t i, std::strin
 // The plan stage, once per handle: d.dpre, d.ent, d.off, d.total, or the error tar_plan gives.
 int plan(pfscdc_ctx* ctx, pfscdc_dev_list* d) {
   ResidentStats& rs = ctx_resident_stats(ctx);
+  const int format = ctx_tar_format(ctx);
+  if (d->planned && d->plan_format != format) {  // laid out under the other format: plan again
+    PFS_HIP(ctx, hipSetDevice(ctx_device(ctx)));
+    for (void** p : {&d->dpre, &d->ent, &d->off, &d->xblk}) {
+      if (*p) PFS_HIP(ctx, hipFree(*p));
+      *p = nullptr;
+    }
+    d->planned = false;
+  }
   rs.n[7] = d->planned ? 1 : 0;
   if (d->planned) return d->plan_rc ? ctx_fail(ctx, d->plan_rc, d->plan_err) : PFSCDC_OK;
   auto done = [&](int rc, const std::string& msg) {
     d->planned = true;
+    d->plan_format = format;
     d->plan_rc = rc;
     d->plan_err = msg;
     return rc ? ctx_fail(ctx, rc, msg) : PFSCDC_OK;
@@ -70,6 +80,14 @@ int plan(pfscdc_ctx* ctx, pfscdc_dev_list* d) {
   PFS_HIP(ctx, off.alloc(sizeof(uint64_t) * (l.n + 1), s));
   PFS_HIP(ctx, flags.alloc(16, s));
   for (const GuardMem* m : {&dsz, &dpre, &ent, &span, &off, &flags}) g.add(*m);
+  const bool pax = format & PFSCDC_TAR_PAX;
+  GuardMem xb, xblk;  // PAX: head blocks other than the main header per entry, and their sums
+  if (pax) {
+    PFS_HIP(ctx, xb.alloc(sizeof(uint64_t) * l.n, s));
+    PFS_HIP(ctx, xblk.alloc(sizeof(uint64_t) * (l.n + 1), s));
+    g.add(xb);
+    g.add(xblk);
+  }
   struct {
     unsigned long long err;
     uint32_t bad, pad;
@@ -77,10 +95,15 @@ int plan(pfscdc_ctx* ctx, pfscdc_dev_list* d) {
   PFS_HIP(ctx, hipMemcpyAsync(flags.p, &h, sizeof h, hipMemcpyHostToDevice, s));
   PFS_HIP(ctx, launch_rtar_sizes(l.drs, l.nr, dsz.as<uint64_t>(), flags.as<uint32_t>() + 2, cus, s));
   PFS_HIP(ctx, launch_rtar_scan(dsz.as<uint64_t>(), l.nr, dpre.as<uint64_t>(), nullptr, s));
-  PFS_HIP(ctx, launch_rtar_entries(l, dpre.as<uint64_t>(), ent.as<TarEntry>(), span.as<uint64_t>(),
+  PFS_HIP(ctx, launch_rtar_entries(l, dpre.as<uint64_t>(), format, ent.as<TarEntry>(),
+                                   span.as<uint64_t>(), pax ? xb.as<uint64_t>() : nullptr,
                                    flags.as<unsigned long long>(), cus, s));
   PFS_HIP(ctx, launch_rtar_scan(span.as<uint64_t>(), l.n, off.as<uint64_t>(), ent.as<TarEntry>(), s));
-  uint64_t at = 0;
+  uint64_t at = 0, nx = 0;
+  if (pax) {
+    PFS_HIP(ctx, launch_rtar_scan(xb.as<uint64_t>(), l.n, xblk.as<uint64_t>(), nullptr, s));
+    PFS_HIP(ctx, hipMemcpyAsync(&nx, xblk.as<uint64_t>() + l.n, sizeof nx, hipMemcpyDeviceToHost, s));
+  }
   PFS_HIP(ctx, hipMemcpyAsync(&h, flags.p, sizeof h, hipMemcpyDeviceToHost, s));
   PFS_HIP(ctx, hipMemcpyAsync(&at, off.as<uint64_t>() + l.n, sizeof at, hipMemcpyDeviceToHost, s));
   PFS_HIP(ctx, g.fetch(s));
@@ -93,7 +116,8 @@ int plan(pfscdc_ctx* ctx, pfscdc_dev_list* d) {
     GuardMem w;
     PFS_HIP(ctx, w.alloc(sizeof(RtarWindow), s));
     RtarWindow hw;
-    PFS_HIP(ctx, launch_rtar_window(l, off.as<uint64_t>(), 1ull << 62, ~0ull, w.as<RtarWindow>(), s));
+    PFS_HIP(ctx, launch_rtar_window(l, off.as<uint64_t>(), nullptr, 1ull << 62, ~0ull,
+                                    w.as<RtarWindow>(), nullptr, s));
     PFS_HIP(ctx, hipMemcpyAsync(&hw, w.p, sizeof hw, hipMemcpyDeviceToHost, s));
     PFS_HIP(ctx, hipStreamSynchronize(s));
     over = hw.i0;  // the last entry whose offset is still <= 2^62
@@ -119,6 +143,12 @@ int plan(pfscdc_ctx* ctx, pfscdc_dev_list* d) {
       case kRtarNoSplit:
         return done(PFSCDC_EUNSUPPORTED, "tar entry " + path + ": a name longer than 100 bytes that does "
                                          "not split needs a PAX header");
+      case kRtarPaxLong:
+        return done(PFSCDC_EUNSUPPORTED, "tar entry " + path + ": a PAX entry's name longer than "
+                                         "65,535 bytes");
+      case kRtarPaxJoin:
+        return done(PFSCDC_EUNSUPPORTED, "tar entry " + path + ": a PAX entry's name that is not "
+                                         "clean (an empty, \".\" or \"..\" component)");
       default: return done(PFSCDC_EINVAL, "tar entry " + path + ": a directory entry with pieces");
     }
   }
@@ -126,6 +156,7 @@ int plan(pfscdc_ctx* ctx, pfscdc_dev_list* d) {
   d->dpre = dpre.release();
   d->ent = ent.release();
   d->off = off.release();
+  d->xblk = nx ? xblk.release() : nullptr;
   d->total = at + 1024;
   return done(PFSCDC_OK, "");
 }
@@ -307,14 +338,21 @@ int pfscdc_dev_list_read_tar(pfscdc_ctx* ctx, const pfscdc_store* store, pfscdc_
   // ---- the entries that meet the window, and their DataRefs
   GuardMem d_w, d_cnt, d_base, d_slices, d_out_off, d_blk, d_runs;
   Guards g;
-  RtarWindow w;
-  PFS_HIP(ctx, d_w.alloc(sizeof(RtarWindow), s));
+  struct {
+    RtarWindow w;
+    uint64_t nx;  // with PAX entries in the list: the window's head blocks besides main headers
+  } hw{};
+  const size_t wbytes = d->xblk ? sizeof hw : sizeof(RtarWindow);
+  PFS_HIP(ctx, d_w.alloc(sizeof hw, s));
   g.add(d_w);
-  PFS_HIP(ctx, launch_rtar_window(l, (const uint64_t*)d->off, begin, end, d_w.as<RtarWindow>(), s));
-  PFS_HIP(ctx, hipMemcpyAsync(&w, d_w.p, sizeof w, hipMemcpyDeviceToHost, s));
+  PFS_HIP(ctx, launch_rtar_window(l, (const uint64_t*)d->off, (const uint64_t*)d->xblk, begin, end,
+                                  d_w.as<RtarWindow>(), d_w.as<uint64_t>() + 4, s));
+  PFS_HIP(ctx, hipMemcpyAsync(&hw, d_w.p, wbytes, hipMemcpyDeviceToHost, s));
   PFS_HIP(ctx, hipStreamSynchronize(s));
-  rs.n[5] += sizeof w;
-  if (w.i0 > w.i1 || w.i1 > l.n || w.k0 > w.k1 || w.k1 > l.nr)
+  rs.n[5] += wbytes;
+  const RtarWindow w = hw.w;
+  // (a name of kTarMaxName bytes has 130 blocks in front of its main header)
+  if (w.i0 > w.i1 || w.i1 > l.n || w.k0 > w.k1 || w.k1 > l.nr || hw.nx > (w.i1 - w.i0) * 130)
     return ctx_fail(ctx, PFSCDC_EHIP, "tar window: the search left the list");
   // ---- pieces: count, scan, fill
   const uint64_t nk = w.k1 - w.k0;
@@ -396,7 +434,7 @@ int pfscdc_dev_list_read_tar(pfscdc_ctx* ctx, const pfscdc_store* store, pfscdc_
   const DevSlices sl{d_slices.as<pfscdc_slice>(), d_out_off.as<uint64_t>(), d_blk.as<uint64_t>(),
                      (uint32_t)m, nblocks};
   const DevTar tar{(const TarEntry*)d->ent + w.i0, (const uint8_t*)d->blob, (uint32_t)(w.i1 - w.i0),
-                   begin, end, total};
+                   begin, end, total, hw.nx ? (const uint64_t*)d->xblk + w.i0 : nullptr, hw.nx};
   if (int rc = read_slices_dev_impl(ctx, b.ct.data(), b.ct.size(), b.offs.data(), nchunks,
                                     b.refs.data(), sl, out, out_on_device, ok.data(), tar,
                                     &rs.n[6], &rs.n[5]))

@@ -1083,7 +1083,8 @@ int pfscdc_store_read_tar(pfscdc_ctx* ctx, const pfscdc_store* s, const pfscdc_t
     sizes[i] = (uint64_t)drs[i].data.size_bytes;
   }
   pfscdc::TarPlan plan;
-  int rc = pfscdc::tar_plan(files, nfiles, sizes.data(), ndrs, begin, len, &plan);
+  int rc = pfscdc::tar_plan(files, nfiles, sizes.data(), ndrs, begin, len,
+                            pfscdc::ctx_tar_format(ctx), &plan);
   if (rc) return pfscdc::ctx_fail(ctx, rc, plan.err);
   const uint64_t window = plan.end - plan.begin;
   if (window > out_cap || (window && !out))

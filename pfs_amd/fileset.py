@@ -53,7 +53,7 @@ def _tar_error(rc: int, what: str):
     if rc == _lib.PFSCDC_EUNSUPPORTED:
         return _lib.PfsCdcError(rc, f"{what}: the entry needs a PAX header (non-ASCII name, a "
                                     "name over 100 bytes that does not split, or a size above "
-                                    "8 GiB - 1), which is not implemented")
+                                    "8 GiB - 1), which is written only with pax=True")
     return ValueError(f"{what}: empty name, or a directory entry with content")
 
 
@@ -71,6 +71,33 @@ def tar_header(path: str, size: int) -> bytes:
     return bytes(out)
 
 
+def _tar_format(pax: bool) -> int:
+    return _lib.TAR_USTAR | _lib.TAR_PAX if pax else _lib.TAR_USTAR
+
+
+def tar_head(path: str, size: int, pax: bool = True) -> bytes:
+    """Every byte in front of an entry's content (pfscdc_tar_head): the 512 bytes of
+    ``tar_header`` for an entry USTAR can hold; with ``pax``, for an entry it cannot hold, what
+    archive/tar's FormatPAX writes: the extended header block, the ``path`` / ``size`` records
+    padded to 512, and the main header block.  PfsCdcError(PFSCDC_EUNSUPPORTED) for an entry
+    that needs PAX without ``pax``, and for a PAX entry whose name has an empty, "." or ".."
+    component; ValueError for an empty name or a directory with a size."""
+    p = path.encode() if isinstance(path, str) else bytes(path)
+    if b"\0" in p or not 0 <= size < 1 << 64:
+        raise ValueError(f"tar entry {path!r}: NUL in the name or a size outside uint64")
+    lib, n = _lib.load(), C.c_uint64()
+    rc = lib.pfscdc_tar_head(p, size, _tar_format(pax), None, 0, C.byref(n))
+    if rc == 0:
+        out = (C.c_uint8 * n.value)()
+        rc = lib.pfscdc_tar_head(p, size, _tar_format(pax), out, n.value, C.byref(n))
+    if rc == _lib.PFSCDC_EUNSUPPORTED and pax:
+        raise _lib.PfsCdcError(rc, f"tar entry {path!r}: a PAX entry's name that is not clean "
+                                   "(or longer than 65,535 bytes)")
+    if rc:
+        raise _tar_error(rc, f"tar entry {path!r}")
+    return bytes(out)
+
+
 def _tar_pieces(files):
     """(path, first, count) triples and the flat DataRef list of [(path, [DataRef])]."""
     triples, flat = [], []
@@ -80,9 +107,9 @@ def _tar_pieces(files):
     return triples, flat
 
 
-def tar_layout(files):
+def tar_layout(files, pax: bool = False):
     """``(entry_offsets, total)`` of the stream getFileTar writes for ``files``, a list of
-    (path, [DataRef]) (pfscdc_tar_layout): entry i is stream bytes [entry_offsets[i],
+    (path, [DataRef]) (pfscdc_tar_layout_format): entry i is stream bytes [entry_offsets[i],
     entry_offsets[i + 1]), the 1,024-byte trailer begins at entry_offsets[len(files)]."""
     triples, flat = _tar_pieces(files)
     tf = _lib.tar_files(triples)
@@ -90,10 +117,11 @@ def tar_layout(files):
         *[sum(d.size_bytes for d in drs) for _, drs in files])
     offs = (C.c_uint64 * (len(files) + 1))()
     total = C.c_uint64()
-    rc = _lib.load().pfscdc_tar_layout(tf, len(files), sizes, offs, C.byref(total))
+    rc = _lib.load().pfscdc_tar_layout_format(tf, len(files), sizes, _tar_format(pax), offs,
+                                              C.byref(total))
     if rc:
         for path, drs in files:  # name the first file that cannot be written
-            tar_header(path, sum(d.size_bytes for d in drs))
+            tar_head(path, sum(d.size_bytes for d in drs), pax)
         raise ValueError("tar_layout: a directory entry with DataRefs")
     return list(offs), total.value
 
@@ -106,14 +134,26 @@ class TarStream:
     formed on the GPU.  ``storage``: a ``chunk.Storage`` with a store; ``files``: a list of
     (path, [DataRef]) in stream order.  Errors as ``chunk.Reader``'s: ValueError, KeyError (a
     chunk missing from the store), PfsCdcError (PFSCDC_ECORRUPT: a chunk failed verification,
-    nothing written; PFSCDC_EUNSUPPORTED: an entry that needs a PAX header)."""
+    nothing written; PFSCDC_EUNSUPPORTED: an entry that needs a PAX header).  ``pax`` (None:
+    the storage's): such an entry is written in PAX format, as archive/tar writes it, instead
+    of being refused; every other entry, and a stream without one, is the same bytes."""
 
-    def __init__(self, storage, files):
+    def __init__(self, storage, files, pax: Optional[bool] = None):
         self.files = [(p, list(drs)) for p, drs in files]
         self.device = storage.device
         self._store = storage.store
-        self.entry_offsets, self._total = tar_layout(self.files)
+        self._set_pax(storage, pax)
+        self.entry_offsets, self._total = tar_layout(self.files, self.pax)
         self._c = None
+
+    def _set_pax(self, storage, pax: Optional[bool]) -> None:
+        self.pax = bool(getattr(storage, "pax", False) if pax is None else pax)
+
+    def _format(self, c) -> None:
+        """This stream's format on the context about to lay it out or read it."""
+        rc = c.lib.pfscdc_set_tar_format(c.ctx, _tar_format(self.pax))
+        if rc:
+            raise _lib.PfsCdcError(rc, "pfscdc_set_tar_format")
 
     def size(self) -> int:
         return self._total
@@ -150,6 +190,7 @@ class TarStream:
         c = chunker if chunker is not None else Chunker(ChunkParams(), self.device)
         try:
             nw = C.c_uint64()
+            self._format(c)
             rc = c.lib.pfscdc_store_read_tar(c.ctx, self._store._s, tf, nfiles, arr,
                                              len(flat), begin, n, ptr, cap, on_device,
                                              C.byref(nw))
@@ -492,15 +533,17 @@ class _DevTarStream(TarStream):
     """TarStream over a resident list: layout and windows through pfscdc_dev_list_tar_layout
     and pfscdc_dev_list_read_tar; nothing per file or per DataRef comes to the host."""
 
-    def __init__(self, storage, dev: DevIndexList):
+    def __init__(self, storage, dev: DevIndexList, pax: Optional[bool] = None):
         self._dev = dev
         self.device = storage.device
         self._store = storage.store
+        self._set_pax(storage, pax)
         self._offsets = None
         self.last_stats = None
         c = Chunker(ChunkParams(), self.device)
         try:
             total = C.c_uint64()
+            self._format(c)
             rc = c.lib.pfscdc_dev_list_tar_layout(c.ctx, dev._p, C.byref(total), None)
             msg = c.lib.pfscdc_last_error(c.ctx)
         finally:
@@ -515,6 +558,7 @@ class _DevTarStream(TarStream):
             c = Chunker(ChunkParams(), self.device)
             try:
                 offs, total = (C.c_uint64 * (len(self._dev) + 1))(), C.c_uint64()
+                self._format(c)
                 rc = c.lib.pfscdc_dev_list_tar_layout(c.ctx, self._dev._p, C.byref(total), offs)
             finally:
                 c.close()
@@ -533,6 +577,7 @@ class _DevTarStream(TarStream):
         c = chunker if chunker is not None else Chunker(ChunkParams(), self.device)
         try:
             nw = C.c_uint64()
+            self._format(c)
             rc = c.lib.pfscdc_dev_list_read_tar(c.ctx, self._store._s, self._dev._p, begin, n, ptr,
                                                 cap, on_device, C.byref(nw))
             msg = c.lib.pfscdc_last_error(c.ctx)
@@ -922,9 +967,9 @@ class _SourceTarStream(_DevTarStream):
     """GetFileTAR as the reference serves it: one tar entry per entry of a source's stream,
     directories included."""
 
-    def __init__(self, storage, source: Source):
+    def __init__(self, storage, source: Source, pax: Optional[bool] = None):
         self._source = source
-        super().__init__(storage, source.list)
+        super().__init__(storage, source.list, pax)
 
 
 class _FlatRefs:
@@ -946,21 +991,23 @@ class _ListTarStream(TarStream):
     """TarStream over a merged IndexList: the list's own pfscdc_tar_file and
     pfscdc_full_dataref arrays go to pfscdc_store_read_tar as they are."""
 
-    def __init__(self, storage, lst: IndexList):
+    def __init__(self, storage, lst: IndexList, pax: Optional[bool] = None):
         self._list = lst
         self.device = storage.device
         self._store = storage.store
+        self._set_pax(storage, pax)
         n, ents, blob, drs, ndr = lst._views()
         lib = lst.lib
         self._tf = lib.pfscdc_index_list_tar_files(lst._p)
         sizes = (C.c_uint64 * max(1, n))(*[ents[i].size_bytes for i in range(n)])
         offs, total = (C.c_uint64 * (n + 1))(), C.c_uint64()
-        rc = lib.pfscdc_tar_layout(self._tf, n, sizes, offs, C.byref(total))
+        rc = lib.pfscdc_tar_layout_format(self._tf, n, sizes, _tar_format(self.pax), offs,
+                                          C.byref(total))
         if rc:
             for i in range(n):  # name the first file that cannot be written
                 e = ents[i]
-                tar_header(blob[e.path_off:e.path_off + e.path_len].decode("utf-8", "replace"),
-                           e.size_bytes)
+                tar_head(blob[e.path_off:e.path_off + e.path_len].decode("utf-8", "replace"),
+                         e.size_bytes, self.pax)
             raise ValueError("tar: a directory entry with DataRefs")
         self.entry_offsets, self._total = list(offs), total.value
         self._c = (self._tf, n, drs, _FlatRefs(lst))
@@ -1006,11 +1053,11 @@ class FileSet:
             raise KeyError(path)
         return ChunkStorage(self._storage.device, store=self._storage.store).new_reader(drs).get()
 
-    def tar(self) -> TarStream:
-        """``GetFileTAR`` over the merged files (a ``TarStream``)."""
+    def tar(self, pax: Optional[bool] = None) -> TarStream:
+        """``GetFileTAR`` over the merged files (a ``TarStream``; ``pax`` as ``TarStream``'s)."""
         if self._dev is not None:
-            return _DevTarStream(self._storage, self._dev)
-        return _ListTarStream(self._storage, self._list)
+            return _DevTarStream(self._storage, self._dev, pax)
+        return _ListTarStream(self._storage, self._list, pax)
 
     # ---- the file RPCs over a Source (driver_file.go:173-385)
 
@@ -1063,12 +1110,13 @@ class FileSet:
         hits = [fi for fi in self._infos(_lib.SRC_SUBTREE, p) if fi.path in (q, q + "/")]
         return hits[-1] if hits else None
 
-    def get_file(self, p: str) -> TarStream:
+    def get_file(self, p: str, pax: Optional[bool] = None) -> TarStream:
         """``getFile`` as ``GetFileTAR`` serves it: what the glob ``p`` matches (each a file, or
         a directory with everything below it) as a ``TarStream`` with one entry per entry of the
         source, directories included.  A ``p`` with none of the glob bytes names one path.
-        KeyError if nothing is there."""
-        return _SourceTarStream(self._storage, self._source(_glob_kind(p), p))
+        KeyError if nothing is there.  ``pax`` (None: the storage's): an entry USTAR cannot
+        hold is written in PAX format instead of PfsCdcError(PFSCDC_EUNSUPPORTED)."""
+        return _SourceTarStream(self._storage, self._source(_glob_kind(p), p), pax)
 
     def glob_file(self, pattern: str) -> list:
         """``globFile``: the ``FileInfo`` of every path the glob ``pattern`` matches itself; a
@@ -1118,13 +1166,17 @@ class Storage:
     one GPU, or with ``devices`` to a device group (one process, several GPUs:
     pfscdc_uw_create_group deals the serialized filesets over them; the filesets and events
     equal one GPU's).  ``store``: the chunk client; with one, every chunk the unordered writers
-    form (data and index) is uploaded into it and ``open`` reads filesets back from it."""
+    form (data and index) is uploaded into it and ``open`` reads filesets back from it.
+    ``pax``: the tar format of every ``TarStream`` opened from it (``FileSet.tar`` /
+    ``get_file``), unless the call says otherwise: False refuses an entry USTAR cannot hold,
+    True writes it in PAX format."""
 
     def __init__(self, device: int = 0, params: ChunkParams = ChunkParams(),
                  mem_threshold: int = DEFAULT_MEMORY_THRESHOLD,
                  index_params: Optional[ChunkParams] = None,
-                 devices: Optional[Sequence[int]] = None, store=None):
+                 devices: Optional[Sequence[int]] = None, store=None, pax: bool = False):
         self.device, self.params = device, params
+        self.pax = pax  # the tar format of everything opened from this storage (TarStream)
         self.devices = list(devices) if devices is not None else None
         self.mem_threshold, self.index_params = mem_threshold, index_params
         self.store = store

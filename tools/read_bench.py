@@ -14,11 +14,12 @@ anything is printed.  Writes one JSON (default profiles/r7/read_path/read_bench.
 
 --tar: the same three layouts as GetFileTAR streams (pfscdc_read_tar, one file per slice),
 alternated in the same process with pfscdc_read_slices over the same slices (the yardstick: its
-code does not change with the tar path).  Per layout: stream bytes, median device ms of the
-verification, the gather and tar_frame_kernel, and read_slices' two figures with their spread.
-The first tar stream of each layout is checked: every file's content against the plaintext,
-sampled headers against pfscdc_tar_header, padding and trailer zero.  Writes
-profiles/r8/read_tar/read_tar.json.
+code does not change with the tar path).  Per layout two lines, one with ASCII names (USTAR
+entries) and one with names that are not ASCII and PAX allowed (every entry a PAX entry): stream
+bytes, median device ms of the verification, the gather and tar_frame_kernel, the wall ms of the
+read_tar call, and read_slices' two figures, with their spreads.  The first tar stream of each
+line is checked: every file's content against the plaintext, sampled heads against
+pfscdc_tar_head, padding and trailer zero.  Writes profiles/r8/read_tar/read_tar.json.
 
 --index: reading a fileset back (pfscdc_index_read).  Two commits are written through the
 unordered writer into a store at the reference's index parameters, 65,536 files of 4 KiB and
@@ -102,6 +103,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -149,74 +151,89 @@ def check(out, data, cb, runs):
     assert at == out.numel()
 
 
-def check_tar(out, data, cb, sl, names, offs, total):
+def check_tar(out, data, cb, sl, names, offs, total, pax=False):
     """The tar stream in out: every file's content is the plaintext of its slice, sampled
-    headers are pfscdc_tar_header's, the sampled files' padding and the trailer are zero."""
-    from pfs_amd.fileset import tar_header
+    heads are pfscdc_tar_head's, the sampled files' padding and the trailer are zero."""
+    from pfs_amd.fileset import tar_head
     chunk, off, size = (sl[k].astype(np.int64) for k in ("chunk", "offset", "size"))
+    hl = len(tar_head(names[0], int(size[0]), pax))  # (the names are equally long)
     for i in range(len(sl)):
-        a, b = int(chunk[i]) * cb + int(off[i]), int(offs[i]) + 512
+        a, b = int(chunk[i]) * cb + int(off[i]), int(offs[i]) + hl
         if not torch.equal(out[b:b + int(size[i])], data[a:a + int(size[i])]):
             raise SystemExit(f"read_bench: tar content differs from the plaintext in file {i}")
     for i in sorted({0, 1, len(sl) // 2, len(sl) - 1} | set(range(0, len(sl), max(1, len(sl) // 61)))):
         at, z = int(offs[i]), int(size[i])
-        if out[at:at + 512].cpu().numpy().tobytes() != tar_header(names[i], z):
-            raise SystemExit(f"read_bench: tar header {i} differs from pfscdc_tar_header")
-        if int(out[at + 512 + z:int(offs[i + 1])].max().item() if -z % 512 else 0) != 0:
+        if out[at:at + hl].cpu().numpy().tobytes() != tar_head(names[i], z, pax):
+            raise SystemExit(f"read_bench: tar head {i} differs from pfscdc_tar_head")
+        if int(out[at + hl + z:int(offs[i + 1])].max().item() if -z % 512 else 0) != 0:
             raise SystemExit(f"read_bench: tar padding of file {i} is not zero")
     if int(out[total - 1024:total].max().item()) != 0:
         raise SystemExit("read_bench: tar trailer is not zero")
 
 
 def tar_rows(args, c, data, ctext, cofs, refs, n, cb):
+    """Per layout two lines: the USTAR stream, and the same files under names that are not
+    ASCII, every entry a PAX entry (names "pax": a three-block head per file)."""
     rows = []
     med = statistics.median
     for name, (sl, ver, runs) in layouts(n, cb, np.random.default_rng(7)).items():
         payload = int(sl["size"].sum())
-        names = ["/bench/%s/%07d" % (name, i) for i in range(len(sl))]
-        files = [(p, i, 1) for i, p in enumerate(names)]
-        padded = (sl["size"].astype(np.int64) + 511) // 512 * 512 + 512
-        offs = np.concatenate([[0], np.cumsum(padded)])
-        total = int(offs[-1]) + 1024
         out = torch.empty(payload, dtype=torch.uint8, device="cuda:0")
-        tout = torch.empty(total, dtype=torch.uint8, device="cuda:0")
-        t_v, t_g, t_f, s_v, s_g = [], [], [], [], []
-        for i in range(args.warmup + args.reps):
-            out.fill_(0xA5)
-            _, cok, _ = c.read_slices(ctext, cofs, refs, sl, out=out, verified=ver)
-            s = c.last_read_timings()
-            if not cok.all():
-                raise SystemExit(f"read_bench: {name}: a chunk failed verification")
-            check(out, data, cb, runs)
-            tout.fill_(0xA5)
-            _, cok, nw = c.read_tar(ctext, cofs, refs, files, sl, out=tout, verified=ver)
-            t = c.last_read_timings()
-            fms = c.last_frame_ms()
-            if not cok.all() or nw != total:
-                raise SystemExit(f"read_bench: {name}: tar read failed")
-            if i == 0:
-                check_tar(tout, data, cb, sl, names, offs, total)
-            if i >= args.warmup:
-                s_v.append(s["verify"])
-                s_g.append(s["gather"])
-                t_v.append(t["verify"])
-                t_g.append(t["gather"])
-                t_f.append(fms)
-        row = {"layout": name, "chunks": n, "chunk_bytes": cb, "files": int(len(sl)),
-               "payload_bytes": payload, "stream_bytes": total,
-               "header_padding_trailer_bytes": total - payload,
-               "tar_verify_ms_median": round(med(t_v), 4),
-               "tar_gather_ms_median": round(med(t_g), 4),
-               "tar_gather_ms_min_max": [round(min(t_g), 4), round(max(t_g), 4)],
-               "tar_frame_ms_median": round(med(t_f), 4),
-               "tar_frame_ms_min_max": [round(min(t_f), 4), round(max(t_f), 4)],
-               "read_slices_verify_ms_median": round(med(s_v), 4),
-               "read_slices_gather_ms_median": round(med(s_g), 4),
-               "read_slices_gather_ms_min_max": [round(min(s_g), 4), round(max(s_g), 4)],
-               "reps": args.reps, "warmup": args.warmup, "first_stream_checked": True}
-        rows.append(row)
-        print(json.dumps(row), flush=True)
-        del out, tout
+        for pax in (False, True):
+            names = [("/bench/%s/é%07d" if pax else "/bench/%s/%07d") % (name, i)
+                     for i in range(len(sl))]
+            files = [(p, i, 1) for i, p in enumerate(names)]
+            head = 1536 if pax else 512  # (a 23-byte name: one block of records)
+            padded = (sl["size"].astype(np.int64) + 511) // 512 * 512 + head
+            offs = np.concatenate([[0], np.cumsum(padded)])
+            total = int(offs[-1]) + 1024
+            tout = torch.empty(total, dtype=torch.uint8, device="cuda:0")
+            t_v, t_g, t_f, t_c, s_v, s_g = [], [], [], [], [], []
+            for i in range(args.warmup + args.reps):
+                out.fill_(0xA5)
+                _, cok, _ = c.read_slices(ctext, cofs, refs, sl, out=out, verified=ver)
+                s = c.last_read_timings()
+                if not cok.all():
+                    raise SystemExit(f"read_bench: {name}: a chunk failed verification")
+                check(out, data, cb, runs)
+                tout.fill_(0xA5)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                _, cok, nw = c.read_tar(ctext, cofs, refs, files, sl, out=tout, verified=ver,
+                                        pax=pax)
+                call_ms = (time.perf_counter() - t0) * 1e3
+                t = c.last_read_timings()
+                fms = c.last_frame_ms()
+                if not cok.all() or nw != total:
+                    raise SystemExit(f"read_bench: {name}: tar read failed")
+                if i == 0:
+                    check_tar(tout, data, cb, sl, names, offs, total, pax)
+                if i >= args.warmup:
+                    s_v.append(s["verify"])
+                    s_g.append(s["gather"])
+                    t_v.append(t["verify"])
+                    t_g.append(t["gather"])
+                    t_f.append(fms)
+                    t_c.append(call_ms)
+            row = {"layout": name, "names": "pax" if pax else "ustar", "chunks": n,
+                   "chunk_bytes": cb, "files": int(len(sl)),
+                   "payload_bytes": payload, "stream_bytes": total,
+                   "header_padding_trailer_bytes": total - payload,
+                   "tar_verify_ms_median": round(med(t_v), 4),
+                   "tar_gather_ms_median": round(med(t_g), 4),
+                   "tar_gather_ms_min_max": [round(min(t_g), 4), round(max(t_g), 4)],
+                   "tar_frame_ms_median": round(med(t_f), 4),
+                   "tar_frame_ms_min_max": [round(min(t_f), 4), round(max(t_f), 4)],
+                   "tar_call_ms_median": round(med(t_c), 3),
+                   "tar_call_ms_min_max": [round(min(t_c), 3), round(max(t_c), 3)],
+                   "read_slices_verify_ms_median": round(med(s_v), 4),
+                   "read_slices_gather_ms_median": round(med(s_g), 4),
+                   "read_slices_gather_ms_min_max": [round(min(s_g), 4), round(max(s_g), 4)],
+                   "reps": args.reps, "warmup": args.warmup, "first_stream_checked": True}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del tout
+        del out
     return rows
 
 
