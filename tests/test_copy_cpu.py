@@ -17,6 +17,7 @@ from pfs_amd import fileset as pf
 import copy_cases as CC
 import copy_oracle as CPO
 import source_cases as SC
+import tree_cases as TC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -163,7 +164,8 @@ def test_a_range_entry_is_refused():
 
 def test_standalone_under_asan_and_ubsan(tmp_path):
     """tests/c/copy_host.cpp with copy_map.cpp and index_decode.cpp, no GPU library, under
-    AddressSanitizer and UBSan: the case table and a random list against the oracle."""
+    AddressSanitizer and UBSan: the case table and a random list against the oracle; and /a of
+    the irregular tree of tests/tree_cases.py copied into itself."""
     rng = random.Random(41)
     cases = [(n,) + CC.table()[n][:4] for n in sorted(CC.table())]
     rnd = CC.random_list(rng, 200)
@@ -178,6 +180,12 @@ def test_standalone_under_asan_and_ubsan(tmp_path):
         wants.append(CC.want_rows(lst, src, dst, tag))
     jobs.append("-\t/a\t\t/z")
     wants.append([])
+    _, _, lst, idx = TC.built(70)
+    f = tmp_path / "irregular.bin"
+    f.write_bytes(b"".join(OF.frame(OF.encode_index(e)) for e in idx))
+    jobs.append("%s\t/a\t\t/a/a!" % f)
+    wants.append(CC.want_rows(lst, "/a", "/a/a!"))
+    assert len(wants[-1]) > 1024
     (tmp_path / "jobs.txt").write_text("\n".join(jobs) + "\n")
     exe = str(tmp_path / "copy_host")
     csrc = os.path.join(ROOT, "pfs_amd", "csrc")

@@ -14,6 +14,7 @@ from pfs_amd import fileset as pf
 
 import diff_oracle as DO
 import source_cases as SC
+import tree_cases as TC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -164,7 +165,8 @@ def test_src_diff_selects_as_subtree_and_never_errs_on_empty():
 def test_standalone_under_asan_and_ubsan(tmp_path):
     """tests/c/diff_host.cpp with diff.cpp and index_decode.cpp, no GPU library, under
     AddressSanitizer and UBSan: empty and NULL sides, the straddle paths, runs of one path,
-    unsorted sides and random trees against the oracle."""
+    unsorted sides and random trees against the oracle; and the irregular tree of
+    tests/tree_cases.py against its changed copy."""
     rng = random.Random(41)
     cases = [([], []), (rows(STRADDLE[0::2]), rows(STRADDLE[1::2])),
              (rows(STRADDLE), rows(STRADDLE, first=1)), (rows(STRADDLE), rows(STRADDLE)),
@@ -188,6 +190,15 @@ def test_standalone_under_asan_and_ubsan(tmp_path):
             names += [str(f), str(g)]
         jobs.append("\t".join(names))
         wants.append(DO.diff([(p, h) for p, _, h in ra], [(p, h) for p, _, h in rb]))
+    names = []
+    for s, side in zip("ab", TC.diff_sides(70)):
+        f, g = tmp_path / ("irregular_%s.bin" % s), tmp_path / ("irregular_%s.hash" % s)
+        f.write_bytes(b"".join(OF.frame(OF.encode_index(e)) for e in side.idx))
+        g.write_bytes(side.leaf)
+        names += [str(f), str(g)]
+    jobs.append("\t".join(names))
+    wants.append(DO.diff(*([(p, h) for p, _, h in side.rows] for side in TC.diff_sides(70))))
+    assert len(wants[-1]) > 1024
     (tmp_path / "jobs.txt").write_text("\n".join(jobs) + "\n")
     exe = str(tmp_path / "diff_host")
     csrc = os.path.join(ROOT, "pfs_amd", "csrc")

@@ -18,6 +18,7 @@ from pfs_amd import fileset as pf
 import glob_oracle as GO
 import source_cases as SC
 import source_oracle as SO
+import tree_cases as TC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -415,7 +416,8 @@ def test_get_with_a_pattern_and_kind_9_are_as_before():
 def test_standalone_under_asan_and_ubsan(tmp_path, table):
     """tests/c/glob_host.cpp with glob.cpp, source.cpp and index_decode.cpp, no GPU library,
     under AddressSanitizer and UBSan: the table, hand and random trees, the error cases, match
-    jobs and the automaton at 1, 63, 64 and 65 positions."""
+    jobs and the automaton at 1, 63, 64 and 65 positions; and two globs over the irregular tree
+    of tests/tree_cases.py, whose deepest path has 71 '/'."""
     rng = random.Random(41)
     trees = [table_tree()] + list(SC.hand_trees().values()) + list(SC.host_only_trees().values()) + \
         [SC.random_tree(rng) for _ in range(20)]
@@ -441,6 +443,12 @@ def test_standalone_under_asan_and_ubsan(tmp_path, table):
                 wants.append(("j", entries, ("unsupported",)))
     jobs.append("s\t-\t%d\t/**" % _lib.SRC_GLOB)
     wants.append(("j", [], ("notfound",)))
+    _, entries, _, idx = TC.built(70)
+    f = tmp_path / "irregular.bin"
+    f.write_bytes(b"".join(OF.frame(OF.encode_index(e)) for e in idx))
+    for g in ("/**/f", "/{a,b}/**0"):
+        jobs.append("s\t%s\t%d\t%s" % (f, _lib.SRC_GLOB, g))
+        wants.append(("j", entries, ("ok", GO.source(entries, g))))
     for _ in range(200):
         arg = GO.random_glob(rng)
         glob = SO.clean_path(arg)

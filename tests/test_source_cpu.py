@@ -16,6 +16,7 @@ from pfs_amd import fileset as pf
 
 import source_cases as SC
 import source_oracle as SO
+import tree_cases as TC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -141,7 +142,8 @@ def test_a_range_entry_is_refused():
 def test_standalone_under_asan_and_ubsan(tmp_path):
     """tests/c/source_host.cpp with source.cpp and index_decode.cpp, no GPU library, under
     AddressSanitizer and UBSan: the hand trees, the host-only lists and random trees, every
-    kind, with and without leaf hashes, against the oracle."""
+    kind, with and without leaf hashes, against the oracle; and the irregular tree of
+    tests/tree_cases.py, whose recursion is 71 directories deep."""
     rng = random.Random(31)
     trees = list(SC.hand_trees().values()) + list(SC.host_only_trees().values()) + \
         [SC.random_tree(rng) for _ in range(40)]
@@ -158,6 +160,13 @@ def test_standalone_under_asan_and_ubsan(tmp_path):
                                                    SC.leaf_of(len(entries)) if with_leaf else None)))
     jobs.append("-\t%d\t0\t/" % SO.ALL)
     wants.append(([], ("ok", [])))
+    _, entries, _, idx = TC.built(70)
+    f = tmp_path / "irregular.bin"
+    f.write_bytes(b"".join(OF.frame(OF.encode_index(e)) for e in idx))
+    for kind, arg, with_leaf in ((SO.ALL, "", 0), (SO.SUBTREE, TC.BUSHES, 1), (SO.GET, "/a", 1)):
+        jobs.append("%s\t%d\t%d\t%s" % (f, kind, with_leaf, arg))
+        wants.append((entries, SC.want(entries, kind, arg,
+                                       SC.leaf_of(len(entries)) if with_leaf else None)))
     (tmp_path / "jobs.txt").write_text("\n".join(jobs) + "\n")
     exe = str(tmp_path / "source_host")
     csrc = os.path.join(ROOT, "pfs_amd", "csrc")
